@@ -6,7 +6,13 @@ One "step" = one pass of the hot path over one synthetic batch through the fused
 configurations, a full training step (training forward + losses + backward + gradient all-reduce +
 Adam) for C5.  Prints ONE JSON line.
 
-  python bench.py [--gpus N --steps K --warmup W] [--config C2|C3|C4|C5]
+  python bench.py [--gpus N --steps K --warmup W] [--config C2|C3|C4|C5] [--full] [--dump-outputs DIR]
+
+A plain run sets up, runs W warm-up steps, times exactly K steps and prints the line (metric, value, unit,
+higher_is_better, dtype, ms_per_step = milliseconds per timed step).  --full adds everything else the benchmark
+measures or checks: the median of five timed blocks, the other arithmetic modes, image renders, training legs, CPU
+baselines, parity against the CPU oracle, the other configurations and the full record.  --dump-outputs DIR writes
+what the timed path computed in its last step as DIR/<name>.npy (float32 / float64, <= 64 MB; inputs are seeded).
 
   --config C2 (default, the headline): blender_refnerf.gin, 4096 rays x 128 samples x 2 levels per GPU (weak scaling)
   --config C3: the "shiny" network (raw_roughness.bias = -6), 8192 rays x 192 samples x 2 levels per GPU (weak)
@@ -91,6 +97,12 @@ def parse():
     ap.add_argument("--no-rccl", action="store_true",
                     help="single-GPU training legs: do not create the one-rank RCCL group (then the gradient all-reduce is skipped as "
                          "torch.distributed is not initialised)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: the median of several timed blocks, the other arithmetic modes, image renders, "
+                         "training legs, CPU baselines, parity checks, other configurations and the full record (the --no-* options "
+                         "trim it).  Without it a run sets up, warms up, times exactly --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -255,6 +267,76 @@ def emit(full):
     out.flush()
 
 
+def emit_line(line):
+    """A plain run's record: the compact line on stdout, nothing else (no full record beside it)."""
+    line = compact_line(line)
+    line.pop("full_record", None)
+    out = _REAL_STDOUT or sys.stdout
+    out.write(json.dumps(line) + "\n")
+    out.flush()
+
+
+DUMP_BYTES = 60 << 20      # array bytes of one --dump-outputs (the .npy headers keep the files under 64 MB in all)
+
+
+def _dump_array(x):
+    """float64 stays float64, other floating types go out as float32, integers and flags as float64 (exact)."""
+    import numpy as np
+    import torch
+    if isinstance(x, torch.Tensor):
+        x = x.detach()
+        x = (x.float() if x.is_floating_point() and x.dtype != torch.float64 else x.double()).contiguous().cpu().numpy()
+    x = np.asarray(x)
+    return x if x.dtype in (np.float32, np.float64) else x.astype(np.float64 if x.dtype.kind in "iub" else np.float32)
+
+
+def dump_outputs(out_dir, arrays, n_rays):
+    """--dump-outputs: {name: tensor} of what the timed path handed its caller in its last step -> out_dir/<name>.npy.  When
+    they exceed DUMP_BYTES, the per-ray arrays (leading dimension n_rays) keep a fixed, seeded sample of the rays, the same
+    for every array and every run with the same arguments; its ray indices go to ray_index.npy."""
+    import numpy as np
+    arrays = {k: _dump_array(v) for k, v in arrays.items()}
+    per_ray = [k for k, a in arrays.items() if a.ndim and a.shape[0] == n_rays]
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BYTES:
+        ray_bytes = sum(arrays[k].nbytes for k in per_ray) // n_rays
+        keep = (DUMP_BYTES - (total - ray_bytes * n_rays)) // (ray_bytes + 8)
+        if keep < 1:
+            raise ValueError(f"--dump-outputs: {total} bytes of outputs, no ray sample fits in {DUMP_BYTES}")
+        idx = np.sort(np.random.default_rng(0).choice(n_rays, keep, replace=False))
+        for k in per_ray:
+            arrays[k] = arrays[k][idx]
+        arrays["ray_index"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return sorted(arrays)
+
+
+def eval_outputs(out):
+    """The (renderings, ray_history) of one Model.__call__ as {name: tensor}: level<l>_rendering_<key>, level<l>_history_<key>."""
+    renderings, history = out
+    arrays = {}
+    for lvl, (rend, hist) in enumerate(zip(renderings, history)):
+        arrays.update({f"level{lvl}_rendering_{k}": v for k, v in rend.items() if v is not None})
+        arrays.update({f"level{lvl}_history_{k}": v for k, v in hist.items() if v is not None})
+    return arrays
+
+
+def train_outputs(model, loss):
+    """What one training step leaves its caller: the loss, and per MLP the flat parameter blob after the Adam step and the
+    (all-reduced) gradient blob it was taken from."""
+    arrays = {"loss": [loss]}
+    for name, mlp in (("nerf_mlp", model.nerf_mlp), ("prop_mlp", model.prop_mlp)):
+        if name == "prop_mlp" and mlp is model.nerf_mlp:
+            continue
+        flat = mlp.flat_params()
+        arrays[name + "_params"] = flat
+        if flat.grad is not None:
+            arrays[name + "_grad"] = flat.grad
+    return arrays
+
+
 # ------------------------------------------------------------------------------------------------ launcher
 def launch_ranks(args) -> int:
     """Parent of `--gpus N` (N > 1) outside torchrun: start one fresh child per GPU and relay rank 0's JSON line.
@@ -330,6 +412,14 @@ def make_rays(spec, n_rays, seed):
     return synthetic.blender_rays(n_rays, seed=seed, center_frac=0.5)
 
 
+def host_cores():
+    """CPUs this process may run on: its affinity mask, capped by OMP_NUM_THREADS when that is set (a shared host's
+    quota).  os.cpu_count() counts the whole machine, and OpenMP pools sized by it only slow themselves down."""
+    n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    omp = os.environ.get("OMP_NUM_THREADS", "")
+    return max(1, min(n, int(omp)) if omp.isdigit() and int(omp) > 0 else n)
+
+
 def cpu_sample_size(spec, cores):
     """FIXED size of the CPU-baseline sample (no calibration runs: the figure used to drift by 40 % with them): the
     first n rays of rank 0's own batch -- the whole batch on a many-core host (~10-20 s), 512 rays otherwise."""
@@ -342,7 +432,7 @@ def cpu_baseline_and_parity(blob, spec, rays_np, hip_outputs):
     of the GPU results of both arithmetic modes on exactly those rays (`parity`)."""
     import numpy as np
     from oracle import oracle as O
-    cores = os.cpu_count() or 1
+    cores = host_cores()
     N = spec["samples"]
     n = cpu_sample_size(spec, cores)
     sub = {k: v[:n] for k, v in rays_np.items()}
@@ -388,7 +478,7 @@ def trained_like_parity(model, cfg, dev, spec, modes, which="trained_blob.npz"):
     rays_np = synthetic.llff_rays(256, seed=3) if llff else synthetic.blender_rays(256, seed=3, center_frac=0.8)
     okw = dict(srgb_mapping=int(model.nerf_mlp.srgb_mapping),
                render_srgb_mode=cfg.srgb_mapping_type if cfg.srgb_mapping_when_rendering else "none")
-    ref = O.model_forward(blob, rays_np, num_prop_samples=N, num_nerf_samples=N, n_threads=os.cpu_count() or 1, history=True, **okw)
+    ref = O.model_forward(blob, rays_np, num_prop_samples=N, num_nerf_samples=N, n_threads=host_cores(), history=True, **okw)
     keep = model.nerf_mlp.flat_params().clone()
     model.nerf_mlp.load_flat_params(blob)
     rays = utils.rays_from_dict(rays_np, dev)
@@ -415,7 +505,7 @@ def cpu_baseline_train(model, cfg, blob, spec, rays_np, rank):
     set are elementwise on the level outputs and are not part of this timing) on a fixed prefix of rank 0's batch."""
     from oracle import oracle as O
     from refnerf_pl_amd import synthetic
-    cores = os.cpu_count() or 1
+    cores = host_cores()
     N = spec["samples"]
     n = min(rays_np["origins"].shape[0], 256 if cores >= 64 else 16)        # (the oracle's training step: ~1e4 ray-samples/s on 256 cores)
     sub = {k: v[:n] for k, v in rays_np.items()}
@@ -446,7 +536,7 @@ def torch_cpu_baseline(spec):
             res = json.loads(r.stdout.strip().splitlines()[-1])
             out.append({"value": res["rate"], "unit": "ray-samples/s", "cores": res["threads"], "kind": "port",
                         "sample": f"unfused PyTorch CPU path, {tag}, eval forward, fp32, {res['seconds']:.2f} s per pass "
-                                  f"(best of {res['tried']} intra-op thread counts <= 64 on {os.cpu_count()} cores: ATen's elementwise ops and "
+                                  f"(best of {res['tried']} intra-op thread counts <= 64 on {host_cores()} cores: ATen's elementwise ops and "
                                   f"small GEMMs get slower, not faster, with hundreds of threads -- 256 threads: > 50 s per pass at C1's shape)"})
         except (subprocess.TimeoutExpired, ValueError, IndexError, KeyError) as e:
             out.append({"value": None, "unit": "ray-samples/s", "cores": None, "kind": "port",
@@ -630,6 +720,7 @@ def main():
     claim_stdout()
     import numpy as np
     import torch
+    torch.manual_seed(0)       # the device-side draws of the step (the noisy rays of C5): identical inputs run to run
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -649,14 +740,15 @@ def main():
             dist.init_process_group(backend)
     dev = torch.device("cuda", local_rank)
     torch.cuda.set_device(dev)
+    spec = dict(CONFIGS[args.config])
     rccl = None
-    if world == 1 and not args.no_rccl:
-        # (eval configurations too since round 5: `n_ranks_seen` of EVERY leg comes from the RCCL group -- VERDICT r4 item 9)
+    if world == 1 and not args.no_rccl and (args.full or spec["mode"] == "train"):
+        # (eval configurations too since round 5: `n_ranks_seen` of EVERY leg comes from the RCCL group -- VERDICT r4 item 9;
+        #  a plain eval run has no collective to issue and skips the group's start-up)
         dist, rccl = one_rank_rccl(dev)
     n_ranks_seen = dist.get_world_size() if dist is not None else 1
     assert n_ranks_seen == world
 
-    spec = dict(CONFIGS[args.config])
     if args.rays:
         spec["rays"] = args.rays
     if args.samples:
@@ -718,14 +810,19 @@ def main():
             return eval_kernel_name(prec, N, rays_per_rank)
 
         step = make_step()
-        # the driver passes --steps 20: ~80 ms of GPU time would be the whole evidence.  The timed block of EXACTLY args.steps
-        # steps (barrier + synchronize on both sides) is therefore repeated N_BLOCKS times and the MEDIAN block is the one
-        # reported (its elapsed time, its event pairs); every block's ms per step travels in the line
-        blocks = [timed(step, args.steps, args.warmup if b == 0 else 0, with_events=not use_graph) for b in range(N_BLOCKS)]
-        order = sorted(range(N_BLOCKS), key=lambda b: blocks[b][0])
-        elapsed, kern_ms, launches, out = blocks[order[N_BLOCKS // 2]]
-        line["timed_blocks"] = {"blocks": N_BLOCKS, "reported": "median", "ms_per_step": [round(1e3 * b[0] / args.steps, 4) for b in blocks]}
-        if use_graph:   # events cannot be recorded inside a graph replay: kernel durations from a short eager pass
+        # the driver passes --steps 20: ~80 ms of GPU time would be the whole evidence.  With --full the timed block of EXACTLY
+        # args.steps steps (barrier + synchronize on both sides) is therefore repeated N_BLOCKS times and the MEDIAN block is the
+        # one reported (its elapsed time, its event pairs); every block's ms per step travels in the line.  A plain run times
+        # one block: exactly args.steps steps
+        n_blocks = N_BLOCKS if args.full else 1
+        blocks = [timed(step, args.steps, args.warmup if b == 0 else 0, with_events=not use_graph) for b in range(n_blocks)]
+        order = sorted(range(n_blocks), key=lambda b: blocks[b][0])
+        elapsed, kern_ms, launches, out = blocks[order[n_blocks // 2]]
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, eval_outputs(blocks[-1][3]), rays_per_rank)     # (the last block ends with the last step)
+        if args.full:
+            line["timed_blocks"] = {"blocks": N_BLOCKS, "reported": "median", "ms_per_step": [round(1e3 * b[0] / args.steps, 4) for b in blocks]}
+        if use_graph and args.full:   # events cannot be recorded inside a graph replay: kernel durations from a short eager pass
             _, kern_ms, launches, _ = timed(eager_step, max(5, args.steps // 10), 2, True)
         rgb = out[0][-1]["rgb"]
         assert torch.isfinite(rgb).all()
@@ -740,7 +837,7 @@ def main():
             line["roofline"] = roofline_of(args.precision, kernel_name(args.precision), kern_ms, launches, flop_per_launch)
         hip_outputs = {args.precision: (out, list(model.last_bin_idx))}
         line["dtype_note"] = MODE_NOTES[args.precision]
-        if rank == 0 and world == 1:
+        if args.full and rank == 0 and world == 1:
             # the other arithmetic modes on the same batch (f32 = exact-fp32 MFMA, the strict parity mode; bf16 / f16 =
             # the two 16-bit MFMA throughput modes)
             def fp64_psnr(x, y):
@@ -761,7 +858,7 @@ def main():
                     "bin_idx_agreement": float((bi[-1] == idx32[-1]).double().mean()),
                     "sdist_max_abs_diff": float((o[1][-1]["sdist"] - ref32[1][-1]["sdist"]).abs().max())}
                 for m, (o, bi) in hip_outputs.items() if m != "f32"}
-        if rank == 0 and world == 1 and not args.no_image and args.config == "C2":
+        if args.full and rank == 0 and world == 1 and not args.no_image and args.config == "C2":
             from refnerf_pl_amd import camera_utils, models, synthetic
             # full-image render ms: 800x800 Blender view, 157 chunks of 4096 rays (models.render_image); the rays of
             # the whole view are cast on the device (refnerf_pixels_to_rays), inside the timed region
@@ -789,24 +886,26 @@ def main():
             line["llff_image_render_ms"] = 1e3 * (time.perf_counter() - t0)
             assert rendering["rgb"].shape == (756, 1008, 3)
             del img, rendering
-        if not args.no_train and args.config == "C2":
+        if args.full and not args.no_train and args.config == "C2":
             line["train_step"] = train_step_bench(args, spec, model, cfg, rays, rank, world, dev, dist, sync, max_over_ranks, "f32")
             line["train_step_f16x2"] = train_step_bench(args, spec, model, cfg, rays, rank, world, dev, dist, sync, max_over_ranks, "f16x2")
             line["train_step_bf16"] = train_step_bench(args, spec, model, cfg, rays, rank, world, dev, dist, sync, max_over_ranks, "bf16")
-        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+        if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"], line["parity"] = cpu_baseline_and_parity(blob, spec, rays_np, hip_outputs)
             line["parity"]["trained_like_weights"] = trained_like_parity(model, cfg, dev, spec, sorted(hip_outputs))
             line["parity"]["trained_long_weights"] = trained_like_parity(model, cfg, dev, spec, sorted(hip_outputs),
                                                                          "trained_llff_blob.npz" if spec["family"] == "llff" else "trained_long_blob.npz")
             if args.config == "C2":
                 line["cpu_baseline_torch"] = torch_cpu_baseline(spec)
-        if rank == 0 and world == 1 and args.config == "C2" and not args.no_other_configs:
+        if args.full and rank == 0 and world == 1 and args.config == "C2" and not args.no_other_configs:
             line["other_configs"] = other_configs(args, dev, sync, max_over_ranks)     # (re-parses the gin config: last)
     else:
         res = train_step_bench(args, spec, model, cfg, rays, rank, world, dev, dist, sync, max_over_ranks,
                                args.train_precision, n_steps=args.steps, n_warm=args.warmup, geometry=True)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, train_outputs(model, res["loss"]), rays_per_rank)
         line["dtype"] = args.train_precision
-        if not args.no_train:
+        if args.full and not args.no_train:
             # the other chain modes beside the headline step: exact fp32 chains (strict parity) and the bf16 throughput mode
             # (its gradient is 1e-1 relative L2 from the reference on trained-like weights)
             for other in [m for m in ("f32", "f16x2", "bf16") if m != args.train_precision]:
@@ -820,10 +919,12 @@ def main():
         line["train_step"] = res
         if rccl is not None:
             line["rccl"] = rccl
-        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+        if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline_train(model, cfg, blob, spec, rays_np, rank)
-    if rank == 0:
+    if rank == 0 and args.full:
         emit(line)
+    elif rank == 0:
+        emit_line(line)
     if dist is not None:
         dist.barrier()
     import torch.distributed as _d

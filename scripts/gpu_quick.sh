@@ -1,11 +1,11 @@
 #!/bin/bash
-# GPU tests (all) + one bench.py line.  usage: scripts/gpu_quick.sh <tag> [bench args]
+# GPU tests (all) + one bench.py --full line.  usage: scripts/gpu_quick.sh <tag> [bench args]
 TAG=${1:-q}; shift
 OUT=gpurun_out/quick_$TAG
 mkdir -p $OUT
 python -m pytest tests -m gpu -q -p no:cacheprovider > $OUT/pytest.log 2>&1; echo "pytest rc=$?"
 grep -E "^FAILED|passed|failed" $OUT/pytest.log | tail -15
-python bench.py --steps 20 --warmup 5 "$@" > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; tail -2 $OUT/bench.err
+python bench.py --full --steps 20 --warmup 5 "$@" > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; tail -2 $OUT/bench.err
 python - <<PY
 import json
 d = json.load(open("$OUT/bench.json"))

@@ -4,7 +4,7 @@
 # REFNERF_BENCH_BACKEND).  usage: scripts/smoke_two_ranks.sh [bench args, e.g. --config C4]
 export REFNERF_BENCH_BACKEND=gloo REFNERF_BENCH_SHARE_GPU=1
 mkdir -p gpurun_out
-timeout -s ABRT 300 python -X faulthandler bench.py --gpus 2 --steps 10 --warmup 3 --no-cpu-baseline --no-image "$@" \
+timeout -s ABRT 300 python -X faulthandler bench.py --full --gpus 2 --steps 10 --warmup 3 --no-cpu-baseline --no-image "$@" \
   > gpurun_out/n2.log 2> gpurun_out/n2.err
 rc=$?
 tail -5 gpurun_out/n2.log
