@@ -95,14 +95,12 @@ enum {
 
 /* element type of the saved layer inputs: fp32 rows (f32 training forward; any forward with a general IPE basis), bf16 rows
  * (bf16-chain training forward, whose activations are bf16-exact: half the stream; rows 2j and 2j+1 share the dwords of
- * pair-row j, low / high half) or split-f16 pair units (REFNERF_ACT_F16X2, the split-f16 training forward on the built-in
- * basis: per pair of rows one dword of packed hi halves and one of packed lo halves, x = hi + lo -- the chain kernels' own
- * B fragments, stored without arithmetic; the split-f16 backward then writes its layer deltas as ONE half per element plus a
- * power-of-two factor per (layer, sample), and the weight-gradient GEMM runs on v_mfma_f32_32x32x16_f16: 26 instead of
- * 34.5 KB of operands per ray-sample).  The buffer is opaque to the caller, only its size is part of the ABI; the 128 rows of
- * ReLU mask words are 32-bit in all three.  refnerf_activations_format(cfg) tells which one refnerf_level_forward_train
+ * pair-row j, low / high half) or REFNERF_ACT_SQ (below).  REFNERF_ACT_F16X2 = 2 is RETIRED: it named the pair units of an
+ * earlier generation of the split-f16 training kernels; the number stays reserved, refnerf_activations_format never returns it
+ * and refnerf_level_backward answers it with REFNERF_EUNSUPPORTED.  The buffer is opaque to the caller, only its size is part
+ * of the ABI.  refnerf_activations_format(cfg) tells which one refnerf_level_forward_train
  * writes for a configuration: pass it on in refnerf_level_saved.activations_format. */
-enum { REFNERF_ACT_F32 = 0, REFNERF_ACT_BF16 = 1, REFNERF_ACT_F16X2 = 2,
+enum { REFNERF_ACT_F32 = 0, REFNERF_ACT_BF16 = 1, REFNERF_ACT_F16X2 = 2 /* retired */,
        REFNERF_ACT_SQ = 3 /* v10: what the REFNERF_PREC_F16X2 training forward writes on the built-in basis: spatial layer inputs as
                              hi / lo pair units, directional layer inputs as the ONE half their trunk multiplies, lane-local ReLU
                              sign words, the raw scalar head rows and raw rgb (13.7 KB per ray-sample; the buffer keeps the size
@@ -295,7 +293,7 @@ int refnerf_activations_format(const refnerf_level_cfg *cfg);   /* REFNERF_ACT_*
 /* v11: the weight image refnerf_level_forward / _forward_train / _backward expect as `d_packed` for this configuration -- the
  * `precision` argument to pass to refnerf_pack_weights (REFNERF_PREC_* or REFNERF_IMAGE_F16X2_TRAIN; a general IPE basis:
  * REFNERF_PREC_F32 through refnerf_pack_weights_basis), -1 for NULL.  One rule, inside the library (it depends on
- * cfg->training, cfg->precision, cfg->ipe_groups and on the REFNERF_LEGACY_F16X2_TRAIN switch the library itself reads).
+ * cfg->training, cfg->precision and cfg->ipe_groups only).
  * The library also remembers, per device pointer, the kind of every image refnerf_pack_weights* wrote: a level entry handed a
  * pointer it packed as ANOTHER kind returns REFNERF_EINVAL instead of streaming garbage (pointers it never packed -- a
  * caller's own copy of an image -- are taken on trust). */

@@ -18,10 +18,9 @@ if os.environ.get("REFNERF_LIB"):      # A/B builds of the library (scripts/buil
 
 PREC_F32, PREC_BF16, PREC_F16, PREC_F16X2 = 0, 1, 2, 3
 IMAGE_F16X2_TRAIN = 4   # REFNERF_IMAGE_F16X2_TRAIN: the weight image of the REFNERF_PREC_F16X2 training kernels (built-in basis)
-ACT_F32, ACT_BF16, ACT_F16X2, ACT_SQ = 0, 1, 2, 3   # REFNERF_ACT_*
+ACT_F32, ACT_BF16, ACT_F16X2, ACT_SQ = 0, 1, 2, 3   # REFNERF_ACT_* (2 is retired: nothing writes or reads it)
 ABI_VERSION = 11  # REFNERF_ABI_VERSION
-# debug knob, read once by the library as well: the round-4 training kernels of the f16x2 mode (REFNERF_ACT_F16X2, f32 image)
-LEGACY_F16X2_TRAIN = os.environ.get("REFNERF_LEGACY_F16X2_TRAIN", "0") not in ("", "0")
+LEGACY_F16X2_TRAIN = False   # the round-4 training kernels (REFNERF_LEGACY_F16X2_TRAIN) are gone; bench.py still reads this name
 WGRAD_F32, WGRAD_BF16X3, WGRAD_F16 = 0, 1, 2
 DIRENC_IDE, DIRENC_POSENC = 0, 1   # REFNERF_DIRENC_*
 RAYDIST = {None: 0, "piecewise": 1, "reciprocal": 2, "log": 3, "exp": 4, "sqrt": 5, "square": 6}   # REFNERF_RAYDIST_*
@@ -176,7 +175,7 @@ def level_image(precision: int, training: bool = False, ipe_groups: int = 0) -> 
     """Which weight image refnerf_level_forward / _forward_train / _backward expect as `d_packed` for a level configuration:
     inference levels the image of their precision mode (a general IPE basis: the f32 image), training levels the f32 image --
     except REFNERF_PREC_F16X2 on the built-in basis, whose training kernels stream their own image (REFNERF_IMAGE_F16X2_TRAIN)."""
-    # one rule, inside the library (ABI v11: refnerf_level_image; it reads the REFNERF_LEGACY_F16X2_TRAIN switch itself)
+    # one rule, inside the library (ABI v11: refnerf_level_image)
     cfg = LevelCfg()
     cfg.precision, cfg.training, cfg.ipe_groups = int(precision), int(bool(training)), int(ipe_groups)
     return int(lib().refnerf_level_image(C.byref(cfg)))
@@ -261,7 +260,7 @@ def level_forward(packed, cfg: LevelCfg, rays: dict, sdist_in, weights_in, histo
         check(lib().refnerf_level_forward_train(ptr(packed), C.byref(cfg), C.byref(rs), R, ptr(sd), ptr(w), C.byref(out),
                                                 ptr(act), act.numel(), stream_ptr()))
         res["activations"] = act
-        # REFNERF_ACT_*: what this forward wrote (f32 rows | bf16 pair-rows | split-f16 hi / lo pair units), as the library says
+        # REFNERF_ACT_*: what this forward wrote (f32 rows | bf16 pair-rows | REFNERF_ACT_SQ), as the library says
         res["activations_format"] = int(lib().refnerf_activations_format(C.byref(cfg)))
     else:
         check(lib().refnerf_level_forward(ptr(packed), C.byref(cfg), C.byref(rs), R, ptr(sd), ptr(w), C.byref(out), stream_ptr()))

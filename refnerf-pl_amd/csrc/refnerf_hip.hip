@@ -29,7 +29,6 @@
 #include "refnerf_level_bwd_f32.h"
 #include "refnerf_wgrad.h"
 #include "refnerf_wgrad_bf16x3.h"
-#include "refnerf_wgrad_f16.h"
 #include "refnerf_rays.h"
 #include "refnerf_pack_common.h"
 #include "refnerf_sq_host.h"
@@ -561,14 +560,6 @@ hipError_t lds_attr(K kernel, int bytes = 160 * 1024) {
     if (attr_err_ != hipSuccess) return fail(REFNERF_EHIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize): %s", hipGetErrorString(attr_err_)); \
   } while (0)
 
-/* REFNERF_LEGACY_F16X2_TRAIN (debug knob, read once): training levels in REFNERF_PREC_F16X2 on the built-in basis take the round-4
- * kernels (fp32 skeleton with split-f16 chains, REFNERF_ACT_F16X2, d_packed = the REFNERF_PREC_F32 image) instead of the
- * round-5 ones (refnerf_sq_train.hip, REFNERF_ACT_SQ, d_packed = the REFNERF_IMAGE_F16X2_TRAIN image) */
-bool legacy_f16x2_train() {
-  static const bool v = [] { const char *e = getenv("REFNERF_LEGACY_F16X2_TRAIN"); return e && *e && *e != '0'; }();
-  return v;
-}
-
 }  // namespace
 
 namespace rnh {
@@ -657,7 +648,7 @@ int check_image(const void *p, const refnerf_level_cfg *cfg, const char *who) {
 int refnerf_level_image(const refnerf_level_cfg *cfg) {
   if (!cfg) return -1;
   if (cfg->ipe_groups > 1) return REFNERF_PREC_F32;
-  if (cfg->training) return (cfg->precision == REFNERF_PREC_F16X2 && !legacy_f16x2_train()) ? REFNERF_IMAGE_F16X2_TRAIN : REFNERF_PREC_F32;
+  if (cfg->training) return cfg->precision == REFNERF_PREC_F16X2 ? REFNERF_IMAGE_F16X2_TRAIN : REFNERF_PREC_F32;
   return cfg->precision;
 }
 
@@ -733,7 +724,7 @@ BwdPlan bwd_plan(int R, int N, int groups = 0) {
   p.delta_off = 0;
   p.part_off = p.delta_off + sizeof(float) * (size_t)rn::DEL_ALLOC_ROWS * p.pitch;
   p.seed_off = p.part_off + sizeof(float) * (size_t)p.slices * rn::NUM_PARAMS;
-  p.cmin_off = p.seed_off + sizeof(float) * (size_t)rn::NGS * p.pitch;      /* split-f16 formats: the smallest factor per layer id */
+  p.cmin_off = p.seed_off + sizeof(float) * (size_t)rn::NGS * p.pitch;      /* REFNERF_ACT_SQ: the smallest delta factor per layer id (kmin of rnsq::wgrad) */
   p.total = p.cmin_off + 128;
   p.act_ext_off = p.act_bytes;
   p.part_ext_off = p.total;
@@ -775,21 +766,20 @@ static int level_forward_impl(const void *d_packed, const refnerf_level_cfg *cfg
   if (!rays->d_origins || !rays->d_directions || !rays->d_viewdirs || !rays->d_radii || !rays->d_near || !rays->d_far)
     return fail(REFNERF_EINVAL, "refnerf_level_forward: null ray field%s");
   const int N = cfg->n_samples;
-  /* training + F16X2: the same kernel with its chains on split-f16 operands (level_fwd_train_f16x2c), fp32 ACT rows */
-  /* (a general basis in F16X2 takes that kernel in inference as well: level_fwd_f16x2c_gb) */
+  /* a general basis in F16X2, training or inference: the fp32-structure kernel with its chains on split-f16 operands
+   * (level_fwd_f16x2c_gb), fp32 ACT rows */
   const bool gb_split = gbasis && cfg->precision == REFNERF_PREC_F16X2;
-  /* training + F16X2 on the built-in basis: the round-5 kernels on the eval kernel's skeleton (refnerf_sq_train.hip);
-   * d_packed is the REFNERF_IMAGE_F16X2_TRAIN image, the activations REFNERF_ACT_SQ */
   if (int irc = check_image(d_packed, cfg, "refnerf_level_forward")) return irc;
-  if (cfg->training && cfg->precision == REFNERF_PREC_F16X2 && !gbasis && !d_act && !legacy_f16x2_train())
+  /* training + F16X2 on the built-in basis: the kernels on the eval kernel's skeleton (refnerf_sq_train.hip);
+   * d_packed is the REFNERF_IMAGE_F16X2_TRAIN image, the activations REFNERF_ACT_SQ */
+  const bool train_sq = cfg->training && cfg->precision == REFNERF_PREC_F16X2 && !gbasis;
+  if (train_sq && !d_act)
     return fail(REFNERF_EINVAL, "a training level in REFNERF_PREC_F16X2 runs through refnerf_level_forward_train: its kernel keeps the ReLU sign words and "
                                 "the bottleneck rows in the activation buffer (d_packed: the REFNERF_IMAGE_F16X2_TRAIN image)%s");
-  if (cfg->wgrad_mode == REFNERF_WGRAD_F16 && !(cfg->training && cfg->precision == REFNERF_PREC_F16X2 && !gbasis && !legacy_f16x2_train()))
+  if (cfg->wgrad_mode == REFNERF_WGRAD_F16 && !train_sq)
     return fail(REFNERF_EUNSUPPORTED, "wgrad_mode = REFNERF_WGRAD_F16 belongs to training levels in REFNERF_PREC_F16X2 on the built-in IPE basis%s");
-  if (cfg->training && cfg->precision == REFNERF_PREC_F16X2 && !gbasis && d_act && !legacy_f16x2_train())
-    return rnsq::forward(d_packed, cfg, rays, R, d_sdist_in, d_weights_in, out, d_act, (hipStream_t)stream);
-  const bool train_split = (cfg->training && cfg->precision == REFNERF_PREC_F16X2) || gb_split;
-  const bool split = cfg->precision == REFNERF_PREC_F16X2 && !train_split;
+  if (train_sq) return rnsq::forward(d_packed, cfg, rays, R, d_sdist_in, d_weights_in, out, d_act, (hipStream_t)stream);
+  const bool split = cfg->precision == REFNERF_PREC_F16X2 && !gb_split;
   const bool bf = (cfg->precision == REFNERF_PREC_BF16 && !train_bf) || cfg->precision == REFNERF_PREC_F16 || split;     /* the LDS-ring 16-bit eval kernels */
   int rpw = rays_per_wg(N, bf ? rn::BT : rn::T_TILE);
   /* 16-bit inference, rays that do not tile the 256-sample pass within 640 samples (N = 192: 2 rays = one and a half
@@ -826,14 +816,12 @@ static int level_forward_impl(const void *d_packed, const refnerf_level_cfg *cfg
   }
   /* bf16 chains: the shared weight-stream ring comes on top; fewer rays per workgroup (a partly filled last pass)
    * when the whole-pass choice no longer fits */
-  /* ... and so do the split-f16 chains of the built-in basis (REFNERF_SPLIT_SHARED: half steps through the same 8 KB slots) */
-  const bool train_ring = train_bf || (train_split && !gbasis && REFNERF_SPLIT_SHARED != 0);
-  while (train_ring && rpw > 1 && (lds + 15) / 16 * 16 + rn::RING_BYTES > 160 * 1024) { rpw /= 2; lds = lds_bytes(rpw); }
+  while (train_bf && rpw > 1 && (lds + 15) / 16 * 16 + rn::RING_BYTES > 160 * 1024) { rpw /= 2; lds = lds_bytes(rpw); }
   const size_t ring_off = (lds + 15) / 16 * 16;
-  if (train_ring) lds = ring_off + rn::RING_BYTES;
+  if (train_bf) lds = ring_off + rn::RING_BYTES;
   lds += (size_t)rt().lds_pad;   /* debug (REFNERF_LDS_PAD): force 1 workgroup/CU */
   if (lds > 160 * 1024) return fail(REFNERF_EINVAL, "n_samples too large for the 160 KiB LDS budget of this precision mode%s");
-  LDS_ATTR_ONCE(lds_attr(rn::level_fwd_f32), lds_attr(rn::level_fwd_train_f32), lds_attr(rn::level_fwd_train_bf16c), lds_attr(rn::level_fwd_train_f16x2c),
+  LDS_ATTR_ONCE(lds_attr(rn::level_fwd_f32), lds_attr(rn::level_fwd_train_f32), lds_attr(rn::level_fwd_train_bf16c),
                 lds_attr(rn::level_fwd_bf16), lds_attr(rn::level_fwd_f16), lds_attr(rn::level_fwd_bf16_ring), lds_attr(rn::level_fwd_f16_ring),
                 lds_attr(rn::level_fwd_f16x2), lds_attr(rn::level_fwd_f16x2_ring), lds_attr(rn::level_fwd_f32_gb), lds_attr(rn::level_fwd_train_f32_gb), lds_attr(rn::level_fwd_f16x2c_gb));
   rn::LevelArgs a;
@@ -868,7 +856,6 @@ static int level_forward_impl(const void *d_packed, const refnerf_level_cfg *cfg
   else if (bf) hipLaunchKernelGGL(rn::level_fwd_bf16, dim3(grid), dim3(rn::BF_NTHREADS), lds, st, a);
   else if (train_bf) hipLaunchKernelGGL(rn::level_fwd_train_bf16c, dim3(grid), dim3(rn::NTHREADS), lds, st, a);
   else if (gb_split) hipLaunchKernelGGL(rn::level_fwd_f16x2c_gb, dim3(grid), dim3(rn::NTHREADS), lds, st, a);
-  else if (train_split) hipLaunchKernelGGL(rn::level_fwd_train_f16x2c, dim3(grid), dim3(rn::NTHREADS), lds, st, a);
   else if (cfg->training && gbasis) hipLaunchKernelGGL(rn::level_fwd_train_f32_gb, dim3(grid), dim3(rn::NTHREADS), lds, st, a);
   else if (cfg->training) hipLaunchKernelGGL(rn::level_fwd_train_f32, dim3(grid), dim3(rn::NTHREADS), lds, st, a);
   else if (gbasis) hipLaunchKernelGGL(rn::level_fwd_f32_gb, dim3(grid), dim3(rn::NTHREADS), lds, st, a);
@@ -993,7 +980,7 @@ size_t refnerf_activation_workspace_bytes_basis(int32_t R, int32_t n_samples, in
 int refnerf_activations_format(const refnerf_level_cfg *cfg) {
   if (!cfg) return -1;
   if (cfg->precision == REFNERF_PREC_BF16) return REFNERF_ACT_BF16;
-  if (cfg->precision == REFNERF_PREC_F16X2 && cfg->ipe_groups <= 1) return legacy_f16x2_train() ? REFNERF_ACT_F16X2 : REFNERF_ACT_SQ;
+  if (cfg->precision == REFNERF_PREC_F16X2 && cfg->ipe_groups <= 1) return REFNERF_ACT_SQ;
   return REFNERF_ACT_F32;
 }
 
@@ -1007,11 +994,12 @@ int refnerf_level_backward(const void *d_packed, const refnerf_level_cfg *cfg, c
   if (cfg->ray_shape != 0 && cfg->ray_shape != 1) return fail(REFNERF_EINVAL, "ray_shape must be 'cone' or 'cylinder'%s");
   if (cfg->precision != REFNERF_PREC_F32 && cfg->precision != REFNERF_PREC_BF16 && cfg->precision != REFNERF_PREC_F16X2)
     return fail(REFNERF_EINVAL, "refnerf_level_backward: unknown precision mode (REFNERF_PREC_F32, REFNERF_PREC_F16X2 or REFNERF_PREC_BF16)%s");
-  if (cfg->precision == REFNERF_PREC_F16X2 && saved->activations_format != REFNERF_ACT_F32 && saved->activations_format != REFNERF_ACT_F16X2 &&
-      saved->activations_format != REFNERF_ACT_SQ)
+  if (saved->activations_format == REFNERF_ACT_F16X2)
+    return fail(REFNERF_EUNSUPPORTED, "activations_format REFNERF_ACT_F16X2 (the split-f16 pair units) is retired: no forward writes it, no backward reads it%s");
+  if (cfg->precision == REFNERF_PREC_F16X2 && saved->activations_format != REFNERF_ACT_F32 && saved->activations_format != REFNERF_ACT_SQ)
     return fail(REFNERF_EUNSUPPORTED, "the split-f16 backward chains read the REFNERF_PREC_F16X2 forward's activations (REFNERF_ACT_SQ) or fp32 rows (REFNERF_PREC_F32, or a general IPE basis)%s");
-  if (cfg->precision != REFNERF_PREC_F16X2 && (saved->activations_format == REFNERF_ACT_F16X2 || saved->activations_format == REFNERF_ACT_SQ))
-    return fail(REFNERF_EUNSUPPORTED, "activations written by the split-f16 training forward (REFNERF_ACT_F16X2) are read by the split-f16 backward: cfg->precision = REFNERF_PREC_F16X2%s");
+  if (cfg->precision != REFNERF_PREC_F16X2 && saved->activations_format == REFNERF_ACT_SQ)
+    return fail(REFNERF_EUNSUPPORTED, "activations written by the split-f16 training forward (REFNERF_ACT_SQ) are read by the split-f16 backward: cfg->precision = REFNERF_PREC_F16X2%s");
   if (cfg->wgrad_mode != REFNERF_WGRAD_F32 && cfg->wgrad_mode != REFNERF_WGRAD_BF16X3 && cfg->wgrad_mode != REFNERF_WGRAD_F16)
     return fail(REFNERF_EINVAL, "refnerf_level_backward: unknown wgrad_mode%s");
   if (cfg->wgrad_mode == REFNERF_WGRAD_F16 && saved->activations_format != REFNERF_ACT_SQ)
@@ -1041,11 +1029,10 @@ int refnerf_level_backward(const void *d_packed, const refnerf_level_cfg *cfg, c
   const int rpw = rays_per_wg(N, rn::T_TILE);
   size_t lds = sizeof(float) * (size_t)(rn::DIR_PAD * rn::T_TILE + rn::HD_ROWS * rn::T_TILE + rpw * (N + 1) + 8);
   const size_t ring_off = (lds + 15) / 16 * 16;
-  if (cfg->precision == REFNERF_PREC_BF16 || (cfg->precision == REFNERF_PREC_F16X2 && saved->activations_format == REFNERF_ACT_F16X2 && REFNERF_SPLIT_SHARED != 0))
+  if (cfg->precision == REFNERF_PREC_BF16)
     lds = ring_off + rn::RING_BYTES;       /* the chains' shared weight-stream ring */
   if (lds > 160 * 1024) return fail(REFNERF_EINVAL, "n_samples too large for the 160 KiB LDS budget%s");
-  LDS_ATTR_ONCE(lds_attr(rn::level_bwd_f32), lds_attr(rn::level_bwd_bf16c), lds_attr(rn::level_bwd_f16x2c), lds_attr(rn::level_bwd_f16x2c_r32),
-                lds_attr(rn::wgrad_f16s_kernel<rn::WF_NW>, rn::wf_lds(rn::WF_NW)),
+  LDS_ATTR_ONCE(lds_attr(rn::level_bwd_f32), lds_attr(rn::level_bwd_bf16c), lds_attr(rn::level_bwd_f16x2c_r32),
                 lds_attr(rn::wgrad_kernel, (rn::WG_TM + rn::WG_TN) * rn::WG_LDK * 4),
                 lds_attr(rn::wgrad_bf16x3_kernel<false, false>, rn::wb_lds(false, false)),
                 lds_attr(rn::wgrad_bf16x3_kernel<false, true>, rn::wb_lds(false, true)),
@@ -1069,18 +1056,15 @@ int refnerf_level_backward(const void *d_packed, const refnerf_level_cfg *cfg, c
   a.seeds = (float *)(ws + plan.seed_off);
   a.pitch = plan.pitch;
   const bool act16 = saved->activations_format == REFNERF_ACT_BF16, del16 = cfg->precision == REFNERF_PREC_BF16 && (REFNERF_DELTA16 != 0);
-  /* split-f16 formats (refnerf_layout.h): ACT as hi / lo pair units, DELTA as one half per element + factor rows */
-  const bool pairs = saved->activations_format == REFNERF_ACT_F16X2;
   const bool sq = saved->activations_format == REFNERF_ACT_SQ;
-  if (saved->activations_format != REFNERF_ACT_F32 && saved->activations_format != REFNERF_ACT_BF16 && !pairs && !sq)
+  if (saved->activations_format != REFNERF_ACT_F32 && saved->activations_format != REFNERF_ACT_BF16 && !sq)
     return fail(REFNERF_EINVAL, "refnerf_level_backward: unknown activations_format%s");
   if (sq && gbasis) return fail(REFNERF_EUNSUPPORTED, "a general IPE basis keeps fp32 activation rows (REFNERF_ACT_F32)%s");
   if (sq && cfg->wgrad_mode != REFNERF_WGRAD_BF16X3 && cfg->wgrad_mode != REFNERF_WGRAD_F16)
     return fail(REFNERF_EUNSUPPORTED, "REFNERF_ACT_SQ activations go with wgrad_mode = REFNERF_WGRAD_BF16X3 (the f16 weight-gradient GEMM on the saved halves; "
                                       "fp32 weight-gradient products: the REFNERF_PREC_F32 chains)%s");
-  if (pairs && gbasis) return fail(REFNERF_EUNSUPPORTED, "a general IPE basis keeps fp32 activation rows (REFNERF_ACT_F32)%s");
-  if ((act16 || del16 || pairs) && cfg->wgrad_mode != REFNERF_WGRAD_BF16X3)
-    return fail(REFNERF_EUNSUPPORTED, "16-bit activation / delta rows (bf16 chains, split-f16 pair units) need wgrad_mode = REFNERF_WGRAD_BF16X3 "
+  if ((act16 || del16) && cfg->wgrad_mode != REFNERF_WGRAD_BF16X3)
+    return fail(REFNERF_EUNSUPPORTED, "16-bit activation / delta rows (bf16 chains) need wgrad_mode = REFNERF_WGRAD_BF16X3 "
                                       "(fp32 weight-gradient products: the REFNERF_PREC_F32 chains)%s");
   a.act16 = act16 ? 1 : 0;
   a.ring_off = (int)ring_off;
@@ -1094,7 +1078,7 @@ int refnerf_level_backward(const void *d_packed, const refnerf_level_cfg *cfg, c
   /* per-ray seeds first (one wave per ray), then the per-sample backward */
   hipLaunchKernelGGL(rn::bwd_seed_kernel, dim3((R + 3) / 4), dim3(rn::NTHREADS), sizeof(float) * 4 * (size_t)(N + 1), st, a);
   if (sq) {
-    /* round-5 kernels: the per-sample chains, then the f16 weight-gradient GEMM on (ACT_SQ, DELTA + factor units) */
+    /* refnerf_sq_train.hip: the per-sample chains, then the f16 weight-gradient GEMM on (ACT_SQ, DELTA + factor units) */
     int rc = rnsq::backward_chain(d_packed, cfg, rays, R, saved->d_sdist, grads, a.act, a.delta, a.seeds, plan.pitch, st);
     if (rc) return rc;
     if (plan.pitch > plan.S) {
@@ -1116,8 +1100,6 @@ int refnerf_level_backward(const void *d_packed, const refnerf_level_cfg *cfg, c
   { int trc = timer_begin(st, &tslot, REFNERF_TIMER_BACKWARD); if (trc) return trc; }
   if (cfg->precision == REFNERF_PREC_BF16)
     hipLaunchKernelGGL(rn::level_bwd_bf16c, dim3((R + rpw - 1) / rpw), dim3(rn::NTHREADS), lds, st, a);
-  else if (cfg->precision == REFNERF_PREC_F16X2 && pairs)
-    hipLaunchKernelGGL(rn::level_bwd_f16x2c, dim3((R + rpw - 1) / rpw), dim3(rn::NTHREADS), lds, st, a);
   else if (cfg->precision == REFNERF_PREC_F16X2)
     hipLaunchKernelGGL(rn::level_bwd_f16x2c_r32, dim3((R + rpw - 1) / rpw), dim3(rn::NTHREADS), lds, st, a);
   else
@@ -1135,26 +1117,18 @@ int refnerf_level_backward(const void *d_packed, const refnerf_level_cfg *cfg, c
   }
   if (plan.pitch > plan.S) {   /* pad columns of both operand matrices must read as zero in the wgrad GEMM */
     hipLaunchKernelGGL(rn::wgrad_zero_tail, dim3(256), dim3(256), 0, st, const_cast<float *>(a.act), act16 ? rn::ACT_ROWS / 2 : rn::ACT_ROWS, rn::act_units(act16), plan.pitch, plan.S);
-    hipLaunchKernelGGL(rn::wgrad_zero_tail, dim3(256), dim3(256), 0, st, a.delta, (del16 || pairs) ? rn::DEL_ROWS / 2 : rn::DEL_ROWS,
-                       pairs ? rn::DEL_UNITS_F16S : rn::del_units(del16), plan.pitch, plan.S);
+    hipLaunchKernelGGL(rn::wgrad_zero_tail, dim3(256), dim3(256), 0, st, a.delta, del16 ? rn::DEL_ROWS / 2 : rn::DEL_ROWS,
+                       rn::del_units(del16), plan.pitch, plan.S);
   }
   rn::WgradArgs w;
-  w.act = a.act; w.delta = a.delta; w.a_units = rn::act_units(act16); w.d_units = pairs ? rn::DEL_UNITS_F16S : rn::del_units(del16); w.pitch = plan.pitch; w.S = plan.S; w.k_per_slice = plan.k_per_slice;
+  w.act = a.act; w.delta = a.delta; w.a_units = rn::act_units(act16); w.d_units = rn::del_units(del16); w.pitch = plan.pitch; w.S = plan.S; w.k_per_slice = plan.k_per_slice;
   w.part = (float *)(ws + plan.part_off);
   const int slices = (int)((plan.S + plan.k_per_slice - 1) / plan.k_per_slice);
   { int trc = timer_begin(st, &tslot, REFNERF_TIMER_WGRAD); if (trc) return trc; }
   if (cfg->wgrad_mode == REFNERF_WGRAD_BF16X3)
   {
     const dim3 wg_grid(8 * ((slices + 7) / 8) * rn::WJOBS.tiles);
-    if (pairs) {
-      /* the layers' smallest factors first (18 exact minima: +inf bits, then one atomicMin per block), then the f16 GEMM */
-      float *cmin = (float *)(ws + plan.cmin_off);
-      HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)cmin, 0x7f800000, 32, st));
-      hipLaunchKernelGGL(rn::delta_scale_min, dim3(rn::DSC_ROWS, 64), dim3(256), 0, st, a.delta, plan.S, cmin);
-      const dim3 wf_grid(8 * ((slices + 7) / 8) * (rn::wf_tm(rn::WF_NW) == 256 ? rn::WJOBS_M256.tiles : rn::WJOBS.tiles));
-      hipLaunchKernelGGL((rn::wgrad_f16s_kernel<rn::WF_NW>), wf_grid, dim3(64 * rn::WF_NW), rn::wf_lds(rn::WF_NW), st, w, slices, cmin);
-    }
-    else if (del16 && act16) hipLaunchKernelGGL((rn::wgrad_bf16x3_kernel<true, true>), wg_grid, dim3(256), rn::wb_lds(true, true), st, w, slices);
+    if (del16 && act16) hipLaunchKernelGGL((rn::wgrad_bf16x3_kernel<true, true>), wg_grid, dim3(256), rn::wb_lds(true, true), st, w, slices);
     else if (del16) hipLaunchKernelGGL((rn::wgrad_bf16x3_kernel<true, false>), wg_grid, dim3(256), rn::wb_lds(true, false), st, w, slices);
     else if (act16) hipLaunchKernelGGL((rn::wgrad_bf16x3_kernel<false, true>), wg_grid, dim3(256), rn::wb_lds(false, true), st, w, slices);
     else hipLaunchKernelGGL((rn::wgrad_bf16x3_kernel<false, false>), wg_grid, dim3(256), rn::wb_lds(false, false), st, w, slices);

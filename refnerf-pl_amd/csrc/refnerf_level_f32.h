@@ -121,24 +121,8 @@ struct RowStoreHookT {
       rs = __builtin_amdgcn_make_buffer_rsrc(base + (unsigned long long)(step >> 4) * blk_bytes, 0, 0x80000000, 0x00020000);
       soff = 0;
     }
-#ifndef REFNERF_EXPERIMENT_NO_STREAM   /* timing experiment only: drops the stream (wrong gradients) */
     if constexpr (H16) __builtin_amdgcn_raw_buffer_store_b16((unsigned short)(__builtin_bit_cast(unsigned, b) >> 16), rs, voff, soff, REFNERF_STREAM_AUX);
     else __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, b), rs, voff, soff, REFNERF_STREAM_AUX);
-#endif
-    soff += ((step & 3) == 3) ? p5 : p1;
-  }
-  /* the same unit walk with a raw dword (REFNERF_ACT_F16X2: units 2j / 2j + 1 = the packed hi / lo halves of rows 2j, 2j + 1,
-   * i.e. step 8 t + e stores dword e >> 1 of the k-step's hi (e even) or lo (e odd) fragment -- no arithmetic, and no float
-   * register in between: a packed pair of halves is not a well-formed float) */
-  __device__ __forceinline__ void raw(int step, unsigned w) {
-    static_assert(!H16, "raw dwords go to 4-byte units");
-    if ((step & 15) == 0 && step > 0) {
-      rs = __builtin_amdgcn_make_buffer_rsrc(base + (unsigned long long)(step >> 4) * blk_bytes, 0, 0x80000000, 0x00020000);
-      soff = 0;
-    }
-#ifndef REFNERF_EXPERIMENT_NO_STREAM
-    __builtin_amdgcn_raw_buffer_store_b32(w, rs, voff, soff, REFNERF_STREAM_AUX);
-#endif
     soff += ((step & 3) == 3) ? p5 : p1;
   }
 };
@@ -167,9 +151,7 @@ struct PairStoreHook {
       rs = __builtin_amdgcn_make_buffer_rsrc(base + (unsigned long long)(j >> 3) * blk_bytes, 0, 0x80000000, 0x00020000);
       soff = 0;
     }
-#ifndef REFNERF_EXPERIMENT_NO_STREAM
     __builtin_amdgcn_raw_buffer_store_b32(dword, rs, voff, soff, REFNERF_STREAM_AUX);
-#endif
     soff += (j & 1) ? p3 : p1;
   }
 };
@@ -398,10 +380,8 @@ __device__ __forceinline__ void gemm_op_split(__amdgpu_buffer_rsrc_t rs, int a_o
       out[ob] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[ob], bl, out[ob], 0, 0, 0);
       if (two) out[ob + 1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[ob + 1], bl, out[ob + 1], 0, 0, 0);
       /* (reads one step past the op at the end: the next op's data or the image's tail pad) */
-#ifndef REFNERF_EXPERIMENT_NO_WSTREAM   /* timing experiment only: the operand stream stops after step 0 (wrong results) */
       fetch(ob, step + 1);
       if (two) fetch(ob + 1, step + 1);
-#endif
       /* the hook's work (8 row stores + their hi + lo sums per k-step) in quarters behind the block pairs: at the end of the
        * step it ran after the last MFMA had issued, i.e. unhidden (one wave per SIMD) */
       if constexpr (NOB == 8) { if (step < REG_STEPS16) hook(step, ob >> 1); }
@@ -418,9 +398,7 @@ __device__ __forceinline__ v4u *smb_slot(const float *act, long long pitch, size
   return reinterpret_cast<v4u *>(base + ((((gs >> 5) * SMB_SLOTS + slot) * 64 + h * 32 + (gs & 31)) << 4));
 }
 __device__ __forceinline__ void smb_store(float *act, long long pitch, size_t gs, int h, int slot, v4u w) {
-#ifndef REFNERF_EXPERIMENT_NO_STREAM
   __builtin_nontemporal_store(w, smb_slot(act, pitch, gs, h, slot));
-#endif
 }
 __device__ __forceinline__ void smb_store_pk(float *act, long long pitch, size_t gs, int h, int slot0, const v4uu (&pk)[16]) {
 #pragma unroll
@@ -533,102 +511,6 @@ __device__ __forceinline__ void gemm_chain_bf16_shared(__amdgpu_buffer_rsrc_t rs
   rendezvous();
 }
 
-/* The same for the split-f16 chains.  A k-step of the split image is [8 hi fragments, 8 KB][8 lo fragments, 8 KB]; the ring
- * keeps its 8 KB slots and works in HALF steps: the even half step brings the hi fragments (16 MFMAs: hi * hi, hi * lo),
- * the odd one the lo fragments (8 MFMAs: lo * hi) -- gemm_op_split's products; an accumulator takes them as hi * hi, hi * lo,
- * lo * hi per k-step instead of hi * hi, lo * hi, hi * lo (fp32 accumulation: results agree to rounding, not bit for bit).  Per-wave streams pull 4 x 16 KB per k-step through the CU's 64 B/clk vector-memory path (1024 cycles
- * against 768 of matrix issue); shared, each wave fetches a quarter.  hook(step, quarter) as gemm_op_split's: quarters
- * 0, 1 ride in the even half step, 2, 3 in the odd one.  Must be called by all four waves, the same number of times. */
-#ifndef REFNERF_SPLIT_SHARED
-#define REFNERF_SPLIT_SHARED 0   /* measured (round 4, C2): forward 6.03 -> 6.20 ms, backward 3.65 -> 3.67: off (docs/EXPERIMENTS.md section 9) */
-#endif
-template <bool BIAS, typename Hook>
-__device__ __forceinline__ void gemm_chain_split_shared(__amdgpu_buffer_rsrc_t rs, int a_off, int b_off, int lane, int h, int wave,
-                                                        const v4uu (&ih)[16], const v4uu (&il)[16], v16f (&out)[8], char *ring, Hook hook) {
-  constexpr int HSTEPS = 32;
-  constexpr int HB = BT_STEP_FLOATS * 4;                        /* 8 KB: [ob][lane][8 f16] */
-  const int voff = wave * 2048 + lane * 16;
-  const int soff = a_off * 4;
-  char *wr = ring + wave * 2048 + lane * 16;
-  const char *rd = ring + lane * 16;
-  auto fetch = [&](int u, v4u (&g)[2]) {
-    g[0] = __builtin_amdgcn_raw_buffer_load_b128(rs, voff, soff + u * HB, 0);
-    g[1] = __builtin_amdgcn_raw_buffer_load_b128(rs, voff + 1024, soff + u * HB, 0);
-  };
-  auto stage = [&](int u, const v4u (&g)[2]) {
-    *reinterpret_cast<v4u *>(wr + (u % RING_SLOTS) * HB) = g[0];
-    *reinterpret_cast<v4u *>(wr + (u % RING_SLOTS) * HB + 1024) = g[1];
-  };
-  auto frags = [&](int u, v8hf (&a)[8]) {
-#pragma unroll
-    for (int ob = 0; ob < 8; ++ob) a[ob] = *reinterpret_cast<const v8hf *>(rd + (u % RING_SLOTS) * HB + ob * 1024);
-  };
-  auto rendezvous = [&]() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-  };
-  constexpr int GD = REFNERF_RING_FETCH;
-  v4u g[GD][2];
-  v8hf a[2][8];
-#pragma unroll
-  for (int d = 0; d < GD; ++d) fetch(d, g[d]);
-  if constexpr (BIAS) load_acc<8>(rs, b_off, h, out);
-  else {
-#pragma unroll
-    for (int ob = 0; ob < 8; ++ob)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) out[ob][r] = 0.0f;
-  }
-  stage(0, g[0]);
-  fetch(GD, g[0]);
-  stage(1, g[1]);
-  fetch(GD + 1, g[1]);
-  rendezvous();
-  frags(0, a[0]);
-  __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-  for (int u = 0; u < HSTEPS; ++u) {
-    const int st = u >> 1;
-    if (u + 1 < HSTEPS) frags(u + 1, a[(u + 1) & 1]);
-    const v8hf bh = __builtin_bit_cast(v8hf, ih[st]), bl = __builtin_bit_cast(v8hf, il[st]);
-    if ((u & 1) == 0) {
-#pragma unroll
-      for (int ob = 0; ob < 8; ++ob) out[ob] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0][ob], bh, out[ob], 0, 0, 0);
-#pragma unroll
-      for (int ob = 0; ob < 8; ++ob) out[ob] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0][ob], bl, out[ob], 0, 0, 0);
-    } else {
-#pragma unroll
-      for (int ob = 0; ob < 8; ++ob) out[ob] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[1][ob], bh, out[ob], 0, 0, 0);
-    }
-    if (u + 2 < HSTEPS) {
-      stage(u + 2, g[(u + 2) % GD]);
-      if (u + 2 + GD < HSTEPS) fetch(u + 2 + GD, g[(u + 2) % GD]);
-    }
-    hook(st, 2 * (u & 1));
-    hook(st, 2 * (u & 1) + 1);
-    /* one wave per SIMD: the fragment reads of the next half step in the first gaps, then the stream's loads, its LDS
-     * writes and the row stores */
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-      __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-    }
-    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-    __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);
-    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-    __builtin_amdgcn_sched_group_barrier(0x200, 2, 0);
-    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-    __builtin_amdgcn_sched_group_barrier(0x040, 2, 0);
-    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-    __builtin_amdgcn_sched_group_barrier(0x040, 2, 0);
-    if (u + 2 < HSTEPS) rendezvous();                 /* the last two half steps' slots are already complete */
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  /* the next call stages into slots 0 and 1 right away: their last readers must be done */
-  rendezvous();
-}
-
 /* ReLU and its sign bit without a compare: as integers, x > 0 <=> max_i32(x, 0) != 0 (negative floats and -0 are
  * negative integers), so relu(x) = max_i32(x, 0) and the mask bit = min_u32(relu(x), 1) -- VALU only (see keep_if_bit),
  * bit-identical to `x > 0 ? x : 0` for every non-NaN x. */
@@ -718,24 +600,22 @@ __device__ __forceinline__ void relu_mask_split(const v16f (&out)[8], unsigned (
  * deltas of a backward chain are 1e-4 .. 1e-9 -- unscaled, their lo halves (and soon the hi halves) underflow and the
  * gradient dies down the chain (measured: 1.0 relative error at the first directional layers).  Columns of the B operand
  * are independent in W^T delta, so every SAMPLE carries its own factor through the chain. */
-/* `live` (optional): whether the sample has any non-zero value at all -- a sample without gradient keeps factor 1, which
- * must not be mistaken for "the sample with the largest deltas" when the layer's smallest factor is taken (refnerf_wgrad_f16.h) */
-__device__ __forceinline__ float pow2_scale_for(float m, bool *live = nullptr) {
+/* (a sample without gradient keeps factor 1) */
+__device__ __forceinline__ float pow2_scale_for(float m) {
   m = fmaxf(m, __shfl_xor(m, 32, 64));                    /* both half-waves hold values of the same sample */
   int e = 8 - __builtin_amdgcn_frexp_expf(m);
   e = e > 100 ? 100 : (e < -100 ? -100 : e);
-  if (live) *live = m > 0.0f;
   return (m > 0.0f) ? __builtin_ldexpf(1.0f, e) : 1.0f;
 }
 /* delta through a recorded ReLU mask into the next transposed GEMM's packed hi / lo fragments, rescaled per sample:
  * on entry `out` carries the factor `c`, on exit the fragments carry the updated `c` (DELTA rows are stored as value / c) */
-__device__ __forceinline__ void mask_split(const v16f (&out)[8], const unsigned (&mk)[4], v4uu (&ph)[16], v4uu (&pl)[16], float &c, bool *live = nullptr) {
+__device__ __forceinline__ void mask_split(const v16f (&out)[8], const unsigned (&mk)[4], v4uu (&ph)[16], v4uu (&pl)[16], float &c) {
   float m = 0.0f;
 #pragma unroll
   for (int ob = 0; ob < 8; ++ob)
 #pragma unroll
     for (int r = 0; r < 16; ++r) m = fmaxf(m, fabsf(keep_if_bit(out[ob][r], mk[ob >> 1], 16 * (ob & 1) + r)));
-  const float rs = pow2_scale_for(m, live);
+  const float rs = pow2_scale_for(m);
   c *= rs;
 #pragma unroll
   for (int ob = 0; ob < 8; ++ob) {
@@ -825,72 +705,6 @@ __device__ __forceinline__ void load_rows(const float *base, long long pitch, in
           x[blk][r + 1] = __builtin_bit_cast(float, w & 0xffff0000u);
         }
       } else x[blk][r] = load_e<false>(base, e0 + (long long)c * pitch);
-    }
-}
-
-/* ---- REFNERF_ACT_F16X2 (refnerf_layout.h): rows in pairs, unit 2j = packed hi halves of rows (2j, 2j + 1), unit 2j + 1 = packed
- * lo halves.  `row` even. ---- */
-__device__ __forceinline__ void stream_store_u(float *base, long long idx, unsigned w) {
-#if REFNERF_STREAM_AUX
-  __builtin_nontemporal_store(w, reinterpret_cast<unsigned *>(base) + idx);
-#else
-  reinterpret_cast<unsigned *>(base)[idx] = w;
-#endif
-}
-__device__ __forceinline__ void store_pair_split(float *base, long long pitch, int row, size_t gs, float x0, float x1) {
-  unsigned hi, lo;
-  split_pair_h(x0, x1, hi, lo);
-  const long long e0 = (long long)row * pitch + (long long)gs;
-  stream_store_u(base, e0, hi);
-  stream_store_u(base, e0 + pitch, lo);
-}
-/* NB accumulator blocks (rows row0 + 32 blk + row(r, h)) as hi / lo pair units */
-template <int NB>
-__device__ __forceinline__ void store_rows_split(float *base, long long pitch, int row0, size_t gs, int h, bool valid, const v16f *x) {
-  const long long e0 = (long long)(row0 + 4 * h) * pitch + (long long)gs;
-  if (valid) {
-#pragma unroll
-    for (int blk = 0; blk < NB; ++blk)
-#pragma unroll
-      for (int r = 0; r < 16; r += 2) {
-        const int c = blk * 32 + (r & 3) + 8 * (r >> 2);
-        unsigned hi, lo;
-        split_pair_h(x[blk][r], x[blk][r + 1], hi, lo);
-        stream_store_u(base, e0 + (long long)c * pitch, hi);
-        stream_store_u(base, e0 + (long long)(c + 1) * pitch, lo);
-      }
-  }
-}
-/* ... and read back as the fp32 accumulator image (hi + lo is exact in fp32) */
-template <int NB>
-__device__ __forceinline__ void load_rows_split(const float *base, long long pitch, int row0, size_t gs, int h, v16f *x) {
-  const long long e0 = (long long)(row0 + 4 * h) * pitch + (long long)gs;
-  const unsigned *u = reinterpret_cast<const unsigned *>(base);
-#pragma unroll
-  for (int blk = 0; blk < NB; ++blk)
-#pragma unroll
-    for (int r = 0; r < 16; r += 2) {
-      const int c = blk * 32 + (r & 3) + 8 * (r >> 2);
-      const unsigned wh = u[e0 + (long long)c * pitch], wl = u[e0 + (long long)(c + 1) * pitch];
-      const v2hf a = __builtin_bit_cast(v2hf, wh), b = __builtin_bit_cast(v2hf, wl);
-      const _Float16 a0 = a[0], a1 = a[1], b0 = b[0], b1 = b[1];
-      x[blk][r] = (float)a0 + (float)b0;
-      x[blk][r + 1] = (float)a1 + (float)b1;
-    }
-}
-
-/* ... or as the packed hi / lo fragments of the 16 k-steps themselves (what the forward's GEMM consumed: dword e of k-step t = the
- * pair units of accumulator rows 2 e, 2 e + 1 of that k-step's block) */
-__device__ __forceinline__ void load_frags_split(const float *base, long long pitch, int row0, size_t gs, int h, v4uu (&fh)[16], v4uu (&fl)[16]) {
-  const long long e0 = (long long)(row0 + 4 * h) * pitch + (long long)gs;
-  const unsigned *u = reinterpret_cast<const unsigned *>(base);
-#pragma unroll
-  for (int t = 0; t < 16; ++t)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int r = 8 * (t & 1) + 2 * e, c = 32 * (t >> 1) + (r & 3) + 8 * (r >> 2);
-      fh[t][e] = u[e0 + (long long)c * pitch];
-      fl[t][e] = u[e0 + (long long)(c + 1) * pitch];
     }
 }
 
@@ -1067,46 +881,8 @@ __device__ __forceinline__ void density_normals_bf16(__amdgpu_buffer_rsrc_t rs, 
   for (int b = 0; b < 3; ++b) nrm_out[b] = -(gx[b] / ng);
 }
 
-/* density_normals on the split-f16 chains: the same VJP with 22-bit deltas; d feature / d mean recomputed exactly as in
+/* density_normals_gb on the split-f16 chains: the same VJP with 22-bit deltas; d feature / d mean recomputed exactly as in
  * the fp32 kernel (ipe_vjp_accum) */
-template <bool SHARED>
-__device__ __forceinline__ void density_normals_split(__amdgpu_buffer_rsrc_t rs, int lane, int h, int wave, char *ring, v16f (&out)[8], v4uu (&ph)[16], v4uu (&pl)[16],
-                                                      unsigned (&M)[8][4], const float lm[3], const float lv[3], float nrm_out[3]) {
-  load_acc<8>(rs, PACKED.wd_off, h, out);
-  float c = 1.0f;                                /* per-sample power-of-two factor the chain carries (mask_split) */
-  mask_split(out, M[7], ph, pl, c);
-  float gl[3] = {0.0f, 0.0f, 0.0f};
-#pragma unroll 1
-  for (int i = 7; i >= 0; --i) {
-    if (i == 5 || i == 0) {
-      v16f gi[3];
-      gemm_op_split<3, 16, 0, false>(rs, PACKED.ht_off[i == 5 ? TOP_SP5_IPE : TOP_SP0], 0, lane, h, ph, pl, gi, nullptr);
-      const float inv = 1.0f / c;
-#pragma unroll
-      for (int blk = 0; blk < 3; ++blk)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) gi[blk][r] *= inv;
-      ipe_vjp_accum(gi, lm, lv, h, gl);
-    }
-    if (i > 0) {
-      if constexpr (SHARED) gemm_chain_split_shared<false>(rs, PACKED.ht_off[i - 1], 0, lane, h, wave, ph, pl, out, ring, NoStepHook());
-      else gemm_op_split<8, 16, 0, false>(rs, PACKED.ht_off[i - 1], 0, lane, h, ph, pl, out, nullptr);
-#pragma unroll
-      for (int l = 7; l > 0; --l)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) M[l][q] = M[l - 1][q];
-      mask_split(out, M[7], ph, pl, c);
-    }
-  }
-#pragma unroll
-  for (int b = 0; b < 3; ++b) gl[b] += __shfl_xor(gl[b], 32, 64);
-  const float gx[3] = {-gl[2], -gl[1], -gl[0]};
-  const float ng = sqrtf(fmaxf((gx[0] * gx[0] + gx[1] * gx[1]) + gx[2] * gx[2], EPS32));
-#pragma unroll
-  for (int b = 0; b < 3; ++b) nrm_out[b] = -(gx[b] / ng);
-}
-
-/* ... and for a general IPE basis (see density_normals_gb) */
 template <typename Lift>
 __device__ __forceinline__ void density_normals_split_gb(__amdgpu_buffer_rsrc_t rs, int lane, int h, v16f (&out)[8], v4uu (&ph)[16], v4uu (&pl)[16],
                                                          unsigned (&M)[8][4], int groups, const float *basis, Lift &&lift, float nrm_out[3]) {
@@ -1156,20 +932,16 @@ __device__ __forceinline__ void density_normals_split_gb(__amdgpu_buffer_rsrc_t 
  * outputs of models.py:533-750 for means / covariances given per sample. */
 /* BFC (training forward only): the MLP chains on v_mfma_f32_32x32x16_bf16 (cfg.precision = BF16 with cfg.training):
  * activations rounded to bf16 once per layer (what ACT then holds), everything per sample fp32. */
-/* SPC (training forward only): the MLP chains on split-f16 operands (cfg.precision = F16X2 with cfg.training): 22-bit
- * products, fp32 everything else, ACT in the fp32 format -- the parity-grade fast training forward. */
+/* SPC (general basis only): the MLP chains on split-f16 operands (cfg.precision = F16X2 with cfg.ipe_groups > 1): 22-bit
+ * products, fp32 everything else, ACT in the fp32 format.  (The built-in basis trains in F16X2 through refnerf_sq_train.hip.) */
 /* GB: general IPE basis (cfg.ipe_groups = G > 1 groups of three directions, refnerf_layout.h): the groups pass through
  * the X tile one after the other in layers 0 and 5, each recomputed from the ray where it is consumed (nothing of it
  * stays live across the trunk) */
 template <bool TRAIN, bool STAGE = false, bool BFC = false, bool SPC = false, bool GB = false>
 __device__ __forceinline__ void level_fwd_f32_body(const LevelArgs &A) {
   static_assert(!BFC || (TRAIN && !STAGE), "bf16 chains: training forward only");
-  static_assert(!SPC || (TRAIN && !STAGE && !BFC), "split-f16 chains: training forward only");
+  static_assert(!SPC || (TRAIN && !STAGE && !BFC && GB), "split-f16 chains: the training-structure forward of a general basis only");
   static_assert(!GB || (!BFC && !(STAGE && SPC)), "general IPE basis: the fp32 skeleton with fp32 or split-f16 chains");
-  /* split chains on the built-in basis save the layer inputs as hi / lo pair units (REFNERF_ACT_F16X2); a general basis keeps
-   * fp32 rows (its tail matrix and tail job table are fp32) */
-  constexpr bool PAIRS = SPC && !GB;
-  constexpr bool SPLIT_RING = SPC && !GB && REFNERF_SPLIT_SHARED != 0;   /* 256 -> 256 chain layers through the shared weight-stream ring */
   extern __shared__ __attribute__((aligned(16))) float smem[];
   RN_STAMP(A, 0);
   const refnerf_level_cfg &cfg = A.cfg;
@@ -1305,20 +1077,12 @@ __device__ __forceinline__ void level_fwd_f32_body(const LevelArgs &A) {
         cast_sample(o, d, radius, t0, t1, cfg.ray_shape, lm, lv);
         if (cfg.disable_integration) { lv[0] = 0.0f; lv[1] = 0.0f; lv[2] = 0.0f; }        /* models.py:228-231 */
       }
-      float fe_prev = 0.0f;
 #pragma unroll 1
       for (int j = 0; j < 16; ++j)
 #pragma unroll
         for (int b = 0; b < 3; ++b) {
           const float fe = ipe_feature<BFC>(lm[b], lv[b], j, h);   /* bf16 chains: hardware sin / exp2, as the bf16 eval kernel (the MLP rounds its inputs to 8 bits) */
           X[(48 * h + j * 3 + b) * T_TILE + col] = fe;
-          if constexpr (PAIRS) {
-            /* features 3 j + b come in row order: every second one completes a pair (rows 48 h + q - 1, 48 h + q) */
-            const int q = j * 3 + b;
-            if (q & 1) { if (save) store_pair_split(A.act, rpitch, ACT_IPE + 48 * h + q - 1, rcol, fe_prev, fe); }
-            else fe_prev = fe;
-            continue;
-          }
           /* bf16 chains: (e sin, e cos) of every (j, b) once more as a bf16 pair in tile rows 128.. (free until P4): the
            * density-normal VJP needs exactly these as d feature / d mean (ipe_vjp_accum_lds) */
           if constexpr (BFC) reinterpret_cast<unsigned short *>(X)[((BNECK + j * 3 + b) * T_TILE + col) * 2 + h] = (unsigned short)cvt_pk_bf16(fe, fe);
@@ -1336,15 +1100,11 @@ __device__ __forceinline__ void level_fwd_f32_body(const LevelArgs &A) {
         for (int e = 0; e < 4; ++e) hk(4 * t + e, pk[t][e]);       /* the k-step's B fragment as it is */
       };
     };
-    auto row_hook = [&](int row0) {              /* split chains: the layer input leaves 8 units per k-step: fp32 rows, or */
+    auto row_hook = [&](int row0) {              /* split chains: the layer input leaves as 8 fp32 rows per k-step (hi + lo is exact) */
       return [&, hk = RowStoreHook(A.act, rpitch, row0, rcol, h, save)](int t, int quarter = -1) mutable {
 #pragma unroll
         for (int e = 0; e < 8; ++e)
-          if (quarter < 0 || (e >> 1) == quarter) {
-            /* (REFNERF_ACT_F16X2) the fragment dwords themselves: unit 2j = hi halves, 2j + 1 = lo halves of rows (2j, 2j + 1) */
-            if constexpr (PAIRS) hk.raw(8 * t + e, (e & 1) ? pl[t][e >> 1] : pk[t][e >> 1]);
-            else hk(8 * t + e, split_elem(pk[t], pl[t], e));
-          }
+          if (quarter < 0 || (e >> 1) == quarter) hk(8 * t + e, split_elem(pk[t], pl[t], e));
       };
     };
     /* general basis: groups 1..G-1 of layer L (0: layer 0, 1: layer 5) accumulate into `out` through the same X rows */
@@ -1360,7 +1120,7 @@ __device__ __forceinline__ void level_fwd_f32_body(const LevelArgs &A) {
     };
     if constexpr (SPC) {
       gemm_op_split<8, 0, BF_IPE_STEPS, true>(rs, PACKED.hf_off[0], PACKED.op[0].b_off, lane, h, pk, pl, out, xc);
-      if constexpr (GB) more_groups(0);
+      more_groups(0);
       relu_mask_split(out, M[7], pk, pl);
     } else if constexpr (BFC) {
       gemm_op_bf16<8, 0, BF_IPE_STEPS, true>(rs, PACKED.bf_off[0], PACKED.op[0].b_off, lane, h, pk, out, xc);
@@ -1383,14 +1143,12 @@ __device__ __forceinline__ void level_fwd_f32_body(const LevelArgs &A) {
     for (int op = 1; op < 8; ++op) {
       /* training: the layer input leaves for the ACT matrix through the store hook (one row per k-step) */
       if constexpr (SPC) {
-        if constexpr (GB) { if (op == 5) { wave_sync(); ipe_group(0, false); wave_sync(); } }     /* X holds the last group of layer 0 */
+        if (op == 5) { wave_sync(); ipe_group(0, false); wave_sync(); }     /* X holds the last group of layer 0 */
         if (op == 5) gemm_op_split<8, 16, BF_IPE_STEPS, true>(rs, PACKED.hf_off[op], PACKED.op[op].b_off, lane, h, pk, pl, out, xc,
                                                              row_hook(ACT_SP + (op - 1) * WIDTH));
-        else if constexpr (SPLIT_RING) gemm_chain_split_shared<true>(rs, PACKED.hf_off[op], PACKED.op[op].b_off, lane, h, wave, pk, pl, out,
-                                                                     reinterpret_cast<char *>(smem) + A.ring_off, row_hook(ACT_SP + (op - 1) * WIDTH));
         else gemm_op_split<8, 16, 0, true>(rs, PACKED.hf_off[op], PACKED.op[op].b_off, lane, h, pk, pl, out, xc,
                                            row_hook(ACT_SP + (op - 1) * WIDTH));
-        if constexpr (GB) { if (op == 5) more_groups(1); }
+        if (op == 5) more_groups(1);
       } else if constexpr (BFC) {
         if (op == 5) gemm_op_bf16<8, 16, BF_IPE_STEPS, true>(rs, PACKED.bf_off[op], PACKED.op[op].b_off, lane, h, pk, out, xc,
                                                             act_hook(ACT_SP + (op - 1) * WIDTH));
@@ -1443,19 +1201,17 @@ __device__ __forceinline__ void level_fwd_f32_body(const LevelArgs &A) {
         int row = (r & 3) + 8 * (r >> 2) + 4 * h;
         if (row < HD_ROWS) X[hdb + row * T_TILE] = hd[4][r];
       }
-      if constexpr (PAIRS) { if (A.act) store_rows_split<4>(A.act, rpitch, ACT_DIN, rcol, h, save, hd); }
-      else if constexpr (TRAIN && !STAGE) { if (A.act) store_rows<4, BFC>(A.act, rpitch, ACT_DIN, rcol, h, save, hd); }
+      if constexpr (TRAIN && !STAGE) { if (A.act) store_rows<4, BFC>(A.act, rpitch, ACT_DIN, rcol, h, save, hd); }
     }
     wave_sync();
 
     SampleHeads sh;
     RN_STAMP(A, 5);
-    if constexpr (SPC && GB) {
+    if constexpr (SPC) {
       /* (this kernel also serves cfg.precision = F16X2 in inference for a general basis: no normals then) */
       if (cfg.training) density_normals_split_gb(rs, lane, h, out, pk, pl, M, cfg.ipe_groups, reinterpret_cast<const float *>(A.packed) + PEXT_BASIS, lift_group, sh.normals);
       else { sh.normals[0] = 0.0f; sh.normals[1] = 0.0f; sh.normals[2] = 0.0f; }
-    } else if constexpr (SPC) density_normals_split<SPLIT_RING>(rs, lane, h, wave, reinterpret_cast<char *>(smem) + A.ring_off, out, pk, pl, M, lm, lv, sh.normals);
-    else if constexpr (BFC) density_normals_bf16(rs, lane, h, wave, reinterpret_cast<char *>(smem) + A.ring_off, out, pk, M, X, col, sh.normals);
+    } else if constexpr (BFC) density_normals_bf16(rs, lane, h, wave, reinterpret_cast<char *>(smem) + A.ring_off, out, pk, M, X, col, sh.normals);
     else if constexpr (TRAIN && GB) density_normals_gb(rs, lane, h, in, out, M, xl, cfg.ipe_groups, reinterpret_cast<const float *>(A.packed) + PEXT_BASIS, lift_group, sh.normals);
     else if constexpr (TRAIN) density_normals(rs, lane, h, in, out, M, lm, lv, xl, sh.normals);
 
@@ -1474,29 +1230,16 @@ __device__ __forceinline__ void level_fwd_f32_body(const LevelArgs &A) {
       float *xi = X + xhi + IDE_TERMS * h * T_TILE;   /* row BNECK (= 128) + 36 h */
       auto put = [&](int q, float val) {
         xi[q * T_TILE] = val;
-        if constexpr (PAIRS) return;             /* pair units: stored from the tile below (the encoders emit out of row order) */
         if constexpr (TRAIN && !STAGE) { if (save) store_row1<BFC>(A.act, rpitch, ACT_DIN + BNECK + IDE_TERMS * h + q, rcol, val); }
       };
       if (cfg.dir_enc == REFNERF_DIRENC_POSENC) posenc_eval(sh.refd[0], sh.refd[1], sh.refd[2], h, put);   /* models.py:487-492 */
       else ide_eval(sh.refd[0], sh.refd[1], sh.refd[2], sh.rough, h, put);
       if (h == 0) {
         X[tile_idx(BNECK + IDE_DIM, col, xhi)] = sh.dot;
-        if constexpr (TRAIN && !STAGE && !PAIRS) { if (save) store_row1<BFC>(A.act, rpitch, ACT_DIN + BNECK + IDE_DIM, rcol, sh.dot); }
+        if constexpr (TRAIN && !STAGE) { if (save) store_row1<BFC>(A.act, rpitch, ACT_DIN + BNECK + IDE_DIM, rcol, sh.dot); }
       } else {
 #pragma unroll
         for (int q = DIR_IN; q < DIR_PAD; ++q) X[tile_idx(q, col, xhi)] = 0.0f;
-      }
-      if constexpr (PAIRS) {
-        /* this lane's own 36 encoder outputs back from the tile, two rows per pair; half 0 adds (n.v, 0) and the (0, 0) pad pair */
-        if (save) {
-#pragma unroll 1
-          for (int q = 0; q < IDE_TERMS; q += 2)
-            store_pair_split(A.act, rpitch, ACT_DIN + BNECK + IDE_TERMS * h + q, rcol, xi[q * T_TILE], xi[(q + 1) * T_TILE]);
-          if (h == 0) {
-            store_pair_split(A.act, rpitch, ACT_DIN + BNECK + IDE_DIM, rcol, sh.dot, 0.0f);
-            store_pair_split(A.act, rpitch, ACT_DIN + BNECK + IDE_DIM + 2, rcol, 0.0f, 0.0f);
-          }
-        }
       }
     }
     wave_sync();
@@ -1526,8 +1269,6 @@ __device__ __forceinline__ void level_fwd_f32_body(const LevelArgs &A) {
       if constexpr (SPC) {
         if (op == 14) gemm_op_split<8, 16, BF_DIN_STEPS, true, decltype(row_hook(0)), DIR_PAD - 1>(
             rs, PACKED.hf_off[op], PACKED.op[op].b_off, lane, h, pk, pl, out, xc, row_hook(ACT_VD + (op - 10) * WIDTH));
-        else if constexpr (SPLIT_RING) gemm_chain_split_shared<true>(rs, PACKED.hf_off[op], PACKED.op[op].b_off, lane, h, wave, pk, pl, out,
-                                                                     reinterpret_cast<char *>(smem) + A.ring_off, row_hook(ACT_VD + (op - 10) * WIDTH));
         else gemm_op_split<8, 16, 0, true>(rs, PACKED.hf_off[op], PACKED.op[op].b_off, lane, h, pk, pl, out, xc,
                                            row_hook(ACT_VD + (op - 10) * WIDTH));
       } else if constexpr (BFC) {
@@ -1583,8 +1324,6 @@ __global__ __launch_bounds__(NTHREADS) void level_fwd_f32(const LevelArgs A) { l
 __global__ __launch_bounds__(NTHREADS) void level_fwd_train_f32(const LevelArgs A) { level_fwd_f32_body<true>(A); }
 /* training forward with the MLP chains on bf16 MFMA (cfg.training && cfg.precision = REFNERF_PREC_BF16) */
 __global__ __launch_bounds__(NTHREADS) void level_fwd_train_bf16c(const LevelArgs A) { level_fwd_f32_body<true, false, true>(A); }
-/* training forward with the MLP chains on split-f16 operands (cfg.training && cfg.precision = REFNERF_PREC_F16X2) */
-__global__ __launch_bounds__(NTHREADS) void level_fwd_train_f16x2c(const LevelArgs A) { level_fwd_f32_body<true, false, false, true>(A); }
 /* eval forward with a general IPE basis (cfg.ipe_groups > 1: icosahedron / tesselated bases) */
 __global__ __launch_bounds__(NTHREADS) void level_fwd_f32_gb(const LevelArgs A) { level_fwd_f32_body<false, false, false, false, true>(A); }
 __global__ __launch_bounds__(NTHREADS) void level_fwd_train_f32_gb(const LevelArgs A) { level_fwd_f32_body<true, false, false, false, true>(A); }

@@ -62,18 +62,6 @@ __device__ __forceinline__ void sq_mask_pack(const v16f &a, v4uu &f0, v4uu &f1, 
 }
 /* the eight dwords of k-steps 2 ob, 2 ob + 1 to their pair rows of DELTA (one half per element) */
 __device__ __forceinline__ void sq_store_delta(const BlkWin &dw, unsigned voff_h2, int unit, const v4uu &f0, const v4uu &f1) {
-#ifdef REFNERF_EXPERIMENT_NO_DELTA   /* timing experiment only: the chains run on real data, their deltas are not written */
-  return;
-#endif
-#ifdef REFNERF_EXPERIMENT_WIDE   /* timing experiment only (wrong layout): the same bytes as two 16-byte stores per lane */
-  {
-    unsigned vo = (voff_h2 & ~255u) + (voff_h2 & 255u) * 4u;
-    asm volatile("" : "+v"(vo));
-    __builtin_amdgcn_raw_buffer_store_b128(f0, dw.rs, vo, unit * 256, REFNERF_SQ_STREAM_AUX);
-    __builtin_amdgcn_raw_buffer_store_b128(f1, dw.rs, vo + 2048u, unit * 256, REFNERF_SQ_STREAM_AUX);
-    return;
-  }
-#endif
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     win_store(dw, voff_h2, unit, 4 * (q >> 1) + (q & 1), f0[q]);

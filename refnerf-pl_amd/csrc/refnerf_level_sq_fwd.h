@@ -53,13 +53,8 @@ __device__ __forceinline__ unsigned blk_voff_add(unsigned voff, int lane_units) 
  * loops -- one VGPR per distinct immediate, 8 to 16 per window, live across every trunk -- and the instruction selector, which
  * works block by block, then finds no add to fold into the immediate field) */
 __device__ __forceinline__ void win_store(const BlkWin &w, unsigned voff, int sunit, int iunit, unsigned dword) {
-#ifndef REFNERF_EXPERIMENT_NO_STREAM
   asm volatile("" : "+v"(voff));
-#ifdef REFNERF_EXPERIMENT_STORE_LOCAL   /* timing experiment only: every store of a lane lands on the same line (no HBM traffic) */
-  sunit &= REFNERF_EXPERIMENT_STORE_LOCAL;
-#endif
   __builtin_amdgcn_raw_buffer_store_b32(dword, w.rs, voff + (unsigned)iunit * 256u, sunit * 256, REFNERF_SQ_STREAM_AUX);
-#endif
 }
 __device__ __forceinline__ unsigned win_load(const BlkWin &w, unsigned voff, int sunit, int iunit) {
   asm volatile("" : "+v"(voff));
@@ -87,11 +82,6 @@ __device__ __forceinline__ void tq_rendezvous(Pipe &p) {
   const long long t2 = (long long)__builtin_readcyclecounter();
   p.t_vm += t1 - t0;
   p.t_bar += t2 - t1;
-#elif defined(REFNERF_EXPERIMENT_TQ_SYNC)   /* timing experiment: the eval kernels' rendezvous (fence + barrier: drains stores and LDS reads) */
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-#elif defined(REFNERF_EXPERIMENT_TQ_LGKM)   /* timing experiment: counted vmcnt, but the LDS reads drained as __syncthreads does */
-  asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(VMK) : "memory");
 #else
   asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(VMK) : "memory");
 #endif
@@ -207,11 +197,6 @@ __device__ __forceinline__ void tq_bf_chunk(Pipe &p, MmF16::v8 (&a)[AF], const v
   auto lds_bq = [&](int kl) { return REAL_L == 1 ? lds_frag<MM>(p.xp) : lds_b<MM, REAL_L>(p, kl); };
   if (KIND == BF_LDS8) { xr[0] = lds_bq(0); xr[1] = lds_bq(1); }
   if (FIRST) acc = bias16(w, p.h);
-#ifdef REFNERF_EXPERIMENT_ACC2
-  v16f acc2;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc2[r] = 0.0f;
-#endif
   __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
   for (int k = 0; k < KS; ++k) {
@@ -220,9 +205,6 @@ __device__ __forceinline__ void tq_bf_chunk(Pipe &p, MmF16::v8 (&a)[AF], const v
     if (lds_step) b = xr[(k - L0) & 1];
     else if (KIND == BF_REG) b = __builtin_bit_cast(v8mm, in[k]);
     else b = __builtin_bit_cast(v8mm, bn[k & 7]);
-#ifdef REFNERF_EXPERIMENT_ACC2
-    if (k & 1) acc2 = MM::mfma(a[k % AF], b, acc2); else
-#endif
     acc = MM::mfma(a[k % AF], b, acc);
     a[k % AF] = (k + AF < KS) ? lds_frag<MM>(cur + (k + AF) * 1024) : lds_frag<MM>(nxt + (k + AF - KS) * 1024);
     if (KIND == BF_LDS8 || KIND == BF_BNLDS) {
@@ -237,10 +219,6 @@ __device__ __forceinline__ void tq_bf_chunk(Pipe &p, MmF16::v8 (&a)[AF], const v
     if (k == RDV + 4) tq_issue<BWD>(p, p.fil_off, 2);
     __builtin_amdgcn_sched_barrier(0);
   }
-#ifdef REFNERF_EXPERIMENT_ACC2
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] += acc2[r];
-#endif
   tq_rotate(p);
 }
 

@@ -63,7 +63,6 @@ constexpr WJobs make_wjobs_t() {
   return J;
 }
 constexpr WJobs WJOBS = make_wjobs_t<WG_TM>();
-constexpr WJobs WJOBS_M256 = make_wjobs_t<256>();
 /* general IPE basis: the tail W_ext[L][256][EXT_K] (refnerf_layout.h) = deltas of layer 0 / 5 x the tail matrix's 576 rows;
  * offsets relative to the tail (its partials and its part of the gradient blob are addressed from NUM_PARAMS on) */
 constexpr WJobs make_wjobs_ext() {

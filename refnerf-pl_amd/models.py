@@ -697,7 +697,7 @@ class Model(nn.Module):
         wgrad = {"f32": _hip.WGRAD_F32, "bf16x3": _hip.WGRAD_BF16X3, "f16": _hip.WGRAD_F16}.get(getattr(cfg, "hip_wgrad_mode", "bf16x3"))
         if wgrad is None:
             raise ValueError("Config.hip_wgrad_mode must be 'bf16x3', 'f16' or 'f32'")
-        if wgrad == _hip.WGRAD_F16 and (not self.training or train_prec != "f16x2" or mlp.ipe_groups or _hip.LEGACY_F16X2_TRAIN):
+        if wgrad == _hip.WGRAD_F16 and (not self.training or train_prec != "f16x2" or mlp.ipe_groups):
             # 'f16' = the weight-gradient GEMM of the split-f16 training kernels with every operand at ONE half: inference levels and
             # the other chain modes (f32 / bf16 chains, a general IPE basis) run the GEMM that goes with them
             wgrad = _hip.WGRAD_BF16X3
@@ -773,7 +773,7 @@ class Model(nn.Module):
                 if bwd_prec == "f16x2" and train_prec == "bf16":
                     raise ValueError("Config.hip_bwd_precision = 'f16x2' reads split-f16 pair units or fp32 rows: use hip_train_precision 'f16x2' or 'f32'")
                 if train_prec == "f16x2" and bwd_prec != "f16x2" and not mlp.ipe_groups:
-                    # the split-f16 training forward saves its layer inputs as hi / lo pair units (REFNERF_ACT_F16X2), which the
+                    # the split-f16 training forward saves its layer inputs in REFNERF_ACT_SQ (packed halves), which the
                     # split-f16 backward and its f16 weight-gradient GEMM consume (a general IPE basis keeps fp32 rows)
                     raise ValueError("Config.hip_train_precision = 'f16x2' goes with hip_bwd_precision = 'f16x2' (its saved activations are "
                                      "split-f16 pair units)")

@@ -1,6 +1,6 @@
 """GPU debug aid: the two levels of test_trained_long_split_chains_equal_f32_chains_from_the_same_step_function (white-noise
 upstream gradients, identical step functions) in the f32 and the f16x2 chain mode through the C ABI, per-tensor gradient
-differences.  Usage: python scripts/dbg_sq_levels.py [tag] [N0 N1]   (REFNERF_LEGACY_F16X2_TRAIN=1: the round-4 kernels).
+differences.  Usage: python scripts/dbg_sq_levels.py [tag] [N0 N1].
 DEBUG INFRASTRUCTURE: never imported by the product."""
 import os
 import sys

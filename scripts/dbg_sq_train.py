@@ -1,7 +1,6 @@
 """GPU debug aid for the round-5 training kernels of the f16x2 mode (refnerf_sq_train.hip): one training step of the smoke
 model in the f32 chains (the strict-parity kernels) and in the f16x2 chains, compared output by output and gradient tensor by
-gradient tensor, plus the oracle's totals.  `REFNERF_LEGACY_F16X2_TRAIN=1 python scripts/dbg_sq_train.py` runs the round-4
-kernels instead.  MEASUREMENT / DEBUG INFRASTRUCTURE: never imported by the product."""
+gradient tensor, plus the oracle's totals.  MEASUREMENT / DEBUG INFRASTRUCTURE: never imported by the product."""
 import os
 import sys
 
@@ -58,7 +57,7 @@ def main():
     rays_t = utils.rays_from_dict(dict(rays_np), dev)
     t32, g32, p32, o32 = run(model, cfg, rays_t, gt, "f32")
     t16, g16, p16, o16 = run(model, cfg, rays_t, gt, "f16x2")
-    print(f"legacy={_hip.LEGACY_F16X2_TRAIN}  total loss f32 {t32:.8f}  f16x2 {t16:.8f}")
+    print(f"total loss f32 {t32:.8f}  f16x2 {t16:.8f}")
     for k in sorted(o32):
         a, b = o32[k], o16[k]
         if a.shape != b.shape:

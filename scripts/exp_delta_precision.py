@@ -5,7 +5,7 @@ nn.Linear computes its WEIGHT / BIAS gradient from rounded copies of its two ope
 is the chain kernels' business):
   ACT   = the layer input  (rows the training forward saves)      -- 'f32' | 'bf16x2' (hi + lo bf16: today's GEMM) | 'f16x2' | 'f16' | 'bf16'
   DELTA = the pre-activation gradient (rows the backward saves)   -- 'f32' | 'bf16x2' | 'bf16' | 'f16s' (ONE f16 after a per-sample
-          power-of-two scale: 11 bits, what level_bwd_f16x2c already holds as its hi halves) | 'f16x2s'
+          power-of-two scale: 11 bits, what the split-f16 backward holds as its hi halves) | 'f16x2s'
 Reported: rel-L2 of the whole gradient against the unrounded autograd, on the trained weight sets' training fixtures.
   python scripts/exp_delta_precision.py
 MEASUREMENT INFRASTRUCTURE: never imported by the product."""

@@ -18,7 +18,7 @@ tag = sys.argv[1]
 d = collections.defaultdict(list)
 for f in glob.glob(f"gpurun_out/pmc_wg_{tag}/**/*counter_collection.csv", recursive=True):
     for r in csv.DictReader(open(f)):
-        if "wgrad_f16s" in r["Kernel_Name"]:
+        if "wgrad_sq" in r["Kernel_Name"]:
             d[r["Counter_Name"]].append(float(r["Counter_Value"]))
 print(tag, {k: "%.4g" % (sum(v) / len(v)) for k, v in d.items()})
 PY

@@ -27,8 +27,6 @@ KERNELS = {"level_fwd_bf16": "rn::level_fwd_bf16", "level_fwd_f32": "rn::level_f
            "bwd_seed_kernel": "rn::bwd_seed_kernel", "wgrad_reduce": "rn::wgrad_reduce",
            "level_fwd_bf16_ring": "rn::level_fwd_bf16_ring", "level_fwd_f16_ring": "rn::level_fwd_f16_ring",
            "level_fwd_f16x2": "rn::level_fwd_f16x2", "level_fwd_f16x2_ring": "rn::level_fwd_f16x2_ring",
-           "level_fwd_train_f16x2c": "rn::level_fwd_train_f16x2c", "level_bwd_f16x2c": "rn::level_bwd_f16x2c",
-           "wgrad_f16s_kernel": "rn::wgrad_f16s_kernel", "delta_scale_min": "rn::delta_scale_min",
            "level_fwd_train_sq": "rn::level_fwd_train_sq", "level_fwd_train_sq_h": "rn::level_fwd_train_sq_h", "level_bwd_sq": "rn::level_bwd_sq",
            "wgrad_sq_kernel": "rn::wgrad_sq_kernel", "wgrad_sq256_kernel": "rn::wgrad_sq256_kernel", "delta_kappa_min": "rn::delta_kappa_min",
            "pack_train_chunks": "rn::pack_train_chunks", "pack_train_consts": "rn::pack_train_consts"}
