@@ -336,8 +336,9 @@ int refnerf_mlp_forward(const void *d_packed, const refnerf_level_cfg *cfg,
                         const refnerf_level_out *out, void *stream);
 
 /* The step in front of the path, on the device: camera_utils.pixels_to_rays
- * (internal/camera_utils.py:502-614) for perspective cameras without lens
- * distortion, with the optional NDC conversion (:31-97, near = 1).
+ * (internal/camera_utils.py:502-614) for perspective cameras (pinhole here;
+ * with lens distortion through refnerf_pixels_to_rays_distorted below), with
+ * the optional NDC conversion (:31-97, near = 1).
  * d_pix_x / d_pix_y [n] int32; d_pixtocams [3,3] (or [n,3,3] when
  * pixtocam_per_ray); d_camtoworlds [3,4] (or [n,3,4]); d_pixtocam_ndc [3,3] or
  * NULL.  Outputs: origins / directions / viewdirs [n,3], radii [n],
@@ -349,6 +350,35 @@ int refnerf_pixels_to_rays(const int32_t *d_pix_x, const int32_t *d_pix_y,
                            const float *d_pixtocam_ndc, int32_t n,
                            float *d_origins, float *d_directions, float *d_viewdirs,
                            float *d_radii, float *d_imageplane, void *stream);
+
+/* Radial-tangential lens distortion: the `distortion_params` dict of the
+ * reference's cameras, i.e. the keyword parameters of
+ * camera_utils._radial_and_tangential_undistort (internal/camera_utils.py:459-470;
+ * reference defaults: coefficients 0, eps 1e-9, max_iterations 10). */
+#define REFNERF_MAX_UNDISTORT_ITERATIONS 64
+typedef struct refnerf_lens_distortion {
+  double k1, k2, k3, k4;  /* radial */
+  double p1, p2;          /* tangential */
+  double eps;             /* a Newton step is taken only where |denominator| > eps */
+  int32_t max_iterations; /* Newton steps, 0 .. REFNERF_MAX_UNDISTORT_ITERATIONS */
+} refnerf_lens_distortion;
+
+/* refnerf_pixels_to_rays with distortion_params (camera_utils.py:558-565): the
+ * three camera-space points of each ray (pixel, +x and +y neighbour) are
+ * undistorted by max_iterations Newton steps in double precision (:409-493),
+ * rounded to float and restacked as (x, y, 1) before the OpenCV -> OpenGL flip;
+ * imageplane, viewdirs, radii and the NDC conversion then see the undistorted
+ * directions.  With all coefficients 0 (or max_iterations 0) and a pixtocam
+ * whose third row is (0, 0, 1) the output is bit-identical to
+ * refnerf_pixels_to_rays.  REFNERF_EINVAL for a NULL `distortion`, a
+ * non-finite coefficient or eps, or max_iterations outside [0, 64]. */
+int refnerf_pixels_to_rays_distorted(const int32_t *d_pix_x, const int32_t *d_pix_y,
+                                     const float *d_pixtocams, int32_t pixtocam_per_ray,
+                                     const float *d_camtoworlds, int32_t camtoworld_per_ray,
+                                     const float *d_pixtocam_ndc, int32_t n,
+                                     float *d_origins, float *d_directions, float *d_viewdirs,
+                                     float *d_radii, float *d_imageplane,
+                                     const refnerf_lens_distortion *distortion, void *stream);
 
 /* Stage entry points (same device code as the fused kernel; used by the
  * parity tests and for drop-in use of the individual reference functions). */

@@ -66,6 +66,11 @@ class LevelGrads(C.Structure):
                                    "d_g_roughness")]
 
 
+class LensDistortion(C.Structure):
+    """refnerf_lens_distortion: the keyword parameters of the reference's _radial_and_tangential_undistort."""
+    _fields_ = [(n, C.c_double) for n in ("k1", "k2", "k3", "k4", "p1", "p2", "eps")] + [("max_iterations", C.c_int32)]
+
+
 class HipLibraryError(RuntimeError):
     pass
 
@@ -115,6 +120,8 @@ def lib():
                                              C.POINTER(LevelSaved), C.POINTER(LevelGrads), _FP, _FP, C.c_size_t, _FP]
         L.refnerf_pixels_to_rays.argtypes = [_FP, _FP, _FP, C.c_int32, _FP, C.c_int32, _FP, C.c_int32,
                                              _FP, _FP, _FP, _FP, _FP, _FP]
+        L.refnerf_pixels_to_rays_distorted.argtypes = [_FP, _FP, _FP, C.c_int32, _FP, C.c_int32, _FP, C.c_int32,
+                                                       _FP, _FP, _FP, _FP, _FP, C.POINTER(LensDistortion), _FP]
         L.refnerf_mlp_forward.argtypes = [_FP, C.POINTER(LevelCfg), _FP, _FP, C.c_int32, _FP, C.c_int32, C.c_int32,
                                           C.POINTER(LevelOut), _FP]
         L.refnerf_sample_intervals.argtypes = [_FP, _FP, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float,
@@ -267,8 +274,9 @@ def level_forward(packed, cfg: LevelCfg, rays: dict, sdist_in, weights_in, histo
     return res
 
 
-def pixels_to_rays(pix_x, pix_y, pixtocams, camtoworlds, pixtocam_ndc=None):
-    """Device tensors in, device tensors out: (origins, directions, viewdirs [n,3], radii [n,1], imageplane [n,2])."""
+def pixels_to_rays(pix_x, pix_y, pixtocams, camtoworlds, pixtocam_ndc=None, distortion: LensDistortion = None):
+    """Device tensors in, device tensors out: (origins, directions, viewdirs [n,3], radii [n,1], imageplane [n,2]).
+    `distortion` (a LensDistortion): undistort first (refnerf_pixels_to_rays_distorted)."""
     require_device()
     dev = pix_x.device
     n = pix_x.numel()
@@ -281,9 +289,12 @@ def pixels_to_rays(pix_x, pix_y, pixtocams, camtoworlds, pixtocam_ndc=None):
     o, d, v = (torch.empty((n, 3), **f32) for _ in range(3))
     r = torch.empty((n, 1), **f32)
     ip = torch.empty((n, 2), **f32)
-    check(lib().refnerf_pixels_to_rays(ptr(px), ptr(py), ptr(p2c), int(p2c.dim() > 2), ptr(c2w), int(c2w.dim() > 2),
-                                       ptr(ndc) if ndc is not None else None, n, ptr(o), ptr(d), ptr(v), ptr(r), ptr(ip),
-                                       stream_ptr()))
+    args = (ptr(px), ptr(py), ptr(p2c), int(p2c.dim() > 2), ptr(c2w), int(c2w.dim() > 2), ptr(ndc) if ndc is not None else None, n,
+            ptr(o), ptr(d), ptr(v), ptr(r), ptr(ip))
+    if distortion is None:
+        check(lib().refnerf_pixels_to_rays(*args, stream_ptr()))
+    else:
+        check(lib().refnerf_pixels_to_rays_distorted(*args, C.byref(distortion), stream_ptr()))
     return o, d, v, r, ip
 
 

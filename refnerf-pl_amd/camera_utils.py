@@ -3,12 +3,15 @@
 Mirrors the call surface of the reference's internal/camera_utils.py for the part
 the Ref-NeRF configs use: `pixels_to_rays` (:502-614), `cast_ray_batch` (:617-670),
 `cast_pinhole_rays` (:673-697), `pixel_coordinates` / `get_pixtocam` (:380-406).
-Perspective cameras without lens distortion; the NDC conversion (:31-97) is
-included.  The arithmetic runs in one HIP kernel (refnerf_pixels_to_rays): pixel
-indices in, the `Rays` fields out, so whole-image rendering neither casts rays
-with numpy on the host nor copies 64 B/ray over PCIe.
+Perspective cameras, with or without radial-tangential lens distortion
+(`distortion_params`, :409-493 and :558-565); the NDC conversion (:31-97) is
+included.  The arithmetic runs in one HIP kernel (refnerf_pixels_to_rays, or
+refnerf_pixels_to_rays_distorted): pixel indices in, the `Rays` fields out, so
+whole-image rendering neither casts rays with numpy on the host nor copies
+64 B/ray over PCIe.
 """
 import enum
+import operator
 
 import numpy as np
 import torch
@@ -43,14 +46,28 @@ def _dev(x, device, dtype=torch.float32):
     return torch.as_tensor(np.asarray(x) if not torch.is_tensor(x) else x, dtype=dtype).to(device)
 
 
+# the keyword parameters of camera_utils._radial_and_tangential_undistort and their defaults (:462-469)
+DISTORTION_DEFAULTS = dict(k1=0., k2=0., k3=0., k4=0., p1=0., p2=0., eps=1e-9, max_iterations=10)
+
+
+def lens_distortion(distortion_params) -> _hip.LensDistortion:
+    """A `distortion_params` dict (shared by all cameras) -> refnerf_lens_distortion.  Missing keys take the reference's
+    defaults; an unknown key raises TypeError, as the reference's `**distortion_params` call does."""
+    unknown = [k for k in distortion_params if k not in DISTORTION_DEFAULTS]
+    if unknown:
+        raise TypeError(f"_radial_and_tangential_undistort() got an unexpected keyword argument {unknown[0]!r}")
+    p = {**DISTORTION_DEFAULTS, **distortion_params}
+    return _hip.LensDistortion(*(float(p[k]) for k in ("k1", "k2", "k3", "k4", "p1", "p2", "eps")),
+                               operator.index(p["max_iterations"]))
+
+
 def pixels_to_rays(pix_x_int, pix_y_int, pixtocams, camtoworlds, distortion_params=None, pixtocam_ndc=None,
                    camtype=ProjectionType.PERSPECTIVE, xnp=torch, device=None):
     """camera_utils.pixels_to_rays: returns (origins, directions, viewdirs [SH,3], radii [SH,1],
     imageplane [SH,2]) as device tensors.  `pixtocams` / `camtoworlds` are one camera ([3,3] / [3,4])
-    or one per pixel (SH + [3,3] / SH + [3,4])."""
+    or one per pixel (SH + [3,3] / SH + [3,4]); `distortion_params` is None or one dict for all of them."""
     del xnp
-    if distortion_params is not None:
-        raise ValueError("lens distortion is outside the fused ray generator (distortion_params must be None)")
+    dist = None if distortion_params is None else lens_distortion(distortion_params)
     if camtype != ProjectionType.PERSPECTIVE:
         raise ValueError("only ProjectionType.PERSPECTIVE cameras are generated on the device")
     if device is None:
@@ -65,7 +82,7 @@ def pixels_to_rays(pix_x_int, pix_y_int, pixtocams, camtoworlds, distortion_para
     if c2w.dim() > 2:
         c2w = torch.broadcast_to(c2w, sh + (3, 4)).reshape(-1, 3, 4)
     ndc = None if pixtocam_ndc is None else _dev(pixtocam_ndc, device)
-    o, d, v, r, ip = _hip.pixels_to_rays(px, py, p2c, c2w, ndc)
+    o, d, v, r, ip = _hip.pixels_to_rays(px, py, p2c, c2w, ndc, distortion=dist)
     return o.reshape(sh + (3,)), d.reshape(sh + (3,)), v.reshape(sh + (3,)), r.reshape(sh + (1,)), ip.reshape(sh + (2,))
 
 

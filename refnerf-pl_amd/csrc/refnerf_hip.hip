@@ -900,23 +900,55 @@ int refnerf_level_forward_train(const void *d_packed, const refnerf_level_cfg *c
   return level_forward_impl(d_packed, cfg, rays, R, d_sdist_in, d_weights_in, out, (float *)d_activations, plan.pitch, stream);
 }
 
-int refnerf_pixels_to_rays(const int32_t *d_pix_x, const int32_t *d_pix_y, const float *d_pixtocams, int32_t pixtocam_per_ray,
-                           const float *d_camtoworlds, int32_t camtoworld_per_ray, const float *d_pixtocam_ndc, int32_t n,
-                           float *d_origins, float *d_directions, float *d_viewdirs, float *d_radii, float *d_imageplane,
-                           void *stream) {
+/* both ray-generation entries; dist == NULL: the pinhole kernel */
+static int pixels_to_rays_impl(const char *fn, const int32_t *d_pix_x, const int32_t *d_pix_y, const float *d_pixtocams,
+                               int32_t pixtocam_per_ray, const float *d_camtoworlds, int32_t camtoworld_per_ray,
+                               const float *d_pixtocam_ndc, int32_t n, float *d_origins, float *d_directions, float *d_viewdirs,
+                               float *d_radii, float *d_imageplane, const refnerf_lens_distortion *dist, void *stream) {
   if (!d_pix_x || !d_pix_y || !d_pixtocams || !d_camtoworlds || !d_origins || !d_directions || !d_viewdirs || !d_radii)
-    return fail(REFNERF_EINVAL, "refnerf_pixels_to_rays: null pointer%s");
-  if (n <= 0) return fail(REFNERF_EINVAL, "refnerf_pixels_to_rays: n must be positive%s");
-  rn::RayGenArgs a;
+    return fail(REFNERF_EINVAL, "%s: null pointer", fn);
+  if (n <= 0) return fail(REFNERF_EINVAL, "%s: n must be positive", fn);
+  rn::RayGenArgs a{};
   a.pix_x = d_pix_x; a.pix_y = d_pix_y;
   a.pixtocams = d_pixtocams; a.camtoworlds = d_camtoworlds; a.pixtocam_ndc = d_pixtocam_ndc;
   a.p2c_stride = pixtocam_per_ray ? 9 : 0;
   a.c2w_stride = camtoworld_per_ray ? 12 : 0;
   a.n = n;
   a.origins = d_origins; a.directions = d_directions; a.viewdirs = d_viewdirs; a.radii = d_radii; a.imageplane = d_imageplane;
-  hipLaunchKernelGGL(rn::pixels_to_rays_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, a);
+  if (dist) {
+    a.dist = {dist->k1, dist->k2, dist->k3, dist->k4, dist->p1, dist->p2, dist->eps, dist->max_iterations};
+    hipLaunchKernelGGL(rn::pixels_to_rays_kernel<true>, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, a);
+  } else {
+    hipLaunchKernelGGL(rn::pixels_to_rays_kernel<false>, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, a);
+  }
   HIP_TRY(hipGetLastError());
   return REFNERF_OK;
+}
+
+int refnerf_pixels_to_rays(const int32_t *d_pix_x, const int32_t *d_pix_y, const float *d_pixtocams, int32_t pixtocam_per_ray,
+                           const float *d_camtoworlds, int32_t camtoworld_per_ray, const float *d_pixtocam_ndc, int32_t n,
+                           float *d_origins, float *d_directions, float *d_viewdirs, float *d_radii, float *d_imageplane,
+                           void *stream) {
+  return pixels_to_rays_impl("refnerf_pixels_to_rays", d_pix_x, d_pix_y, d_pixtocams, pixtocam_per_ray, d_camtoworlds,
+                             camtoworld_per_ray, d_pixtocam_ndc, n, d_origins, d_directions, d_viewdirs, d_radii, d_imageplane,
+                             nullptr, stream);
+}
+
+int refnerf_pixels_to_rays_distorted(const int32_t *d_pix_x, const int32_t *d_pix_y, const float *d_pixtocams,
+                                     int32_t pixtocam_per_ray, const float *d_camtoworlds, int32_t camtoworld_per_ray,
+                                     const float *d_pixtocam_ndc, int32_t n, float *d_origins, float *d_directions,
+                                     float *d_viewdirs, float *d_radii, float *d_imageplane,
+                                     const refnerf_lens_distortion *distortion, void *stream) {
+  if (!distortion) return fail(REFNERF_EINVAL, "refnerf_pixels_to_rays_distorted: null distortion%s");
+  const double c[7] = {distortion->k1, distortion->k2, distortion->k3, distortion->k4, distortion->p1, distortion->p2,
+                       distortion->eps};
+  for (double v : c)
+    if (!std::isfinite(v)) return fail(REFNERF_EINVAL, "refnerf_pixels_to_rays_distorted: non-finite distortion parameter%s");
+  if (distortion->max_iterations < 0 || distortion->max_iterations > REFNERF_MAX_UNDISTORT_ITERATIONS)
+    return fail(REFNERF_EINVAL, "refnerf_pixels_to_rays_distorted: max_iterations must be in [0, 64]%s");
+  return pixels_to_rays_impl("refnerf_pixels_to_rays_distorted", d_pix_x, d_pix_y, d_pixtocams, pixtocam_per_ray,
+                             d_camtoworlds, camtoworld_per_ray, d_pixtocam_ndc, n, d_origins, d_directions, d_viewdirs,
+                             d_radii, d_imageplane, distortion, stream);
 }
 
 int refnerf_mlp_forward(const void *d_packed, const refnerf_level_cfg *cfg, const float *d_means, const float *d_covs,

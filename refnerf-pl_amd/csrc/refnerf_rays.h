@@ -1,14 +1,21 @@
 /*
  * refnerf_rays.h -- on-device ray generation: the step in front of the path
  * (camera_utils.pixels_to_rays, internal/camera_utils.py:502-614, perspective
- * cameras without lens distortion; optional NDC conversion,
- * camera_utils.convert_to_ndc :31-97).  One thread per pixel; 8 B in
- * (pixel coordinates), 56 B out per ray -- HBM-bound, trivially so.
+ * cameras, optionally with radial-tangential lens undistortion, :409-493 and
+ * :558-565; optional NDC conversion, camera_utils.convert_to_ndc :31-97).  One
+ * thread per pixel; 8 B in (pixel coordinates), 56 B out per ray -- HBM-bound,
+ * trivially so for the pinhole instantiation.
  */
 #pragma once
 #include <hip/hip_runtime.h>
 
 namespace rn {
+
+/* the keyword parameters of camera_utils._radial_and_tangential_undistort (:459-470) */
+struct LensDistortion {
+  double k1, k2, k3, k4, p1, p2, eps;
+  int max_iterations;
+};
 
 struct RayGenArgs {
   const int *pix_x, *pix_y;
@@ -18,7 +25,34 @@ struct RayGenArgs {
   int p2c_stride, c2w_stride;
   int n;
   float *origins, *directions, *viewdirs, *radii, *imageplane;
+  LensDistortion dist;      /* read by the distorted instantiation only */
 };
+
+/* camera_utils._radial_and_tangential_undistort on one point, in double (the reference's dataset path
+ * computes in float64): Newton on the residual / Jacobian of _compute_residual_and_jacobian (:409-456),
+ * in the reference's operation order; the step is taken only where |denominator| > eps (:480-491). */
+__device__ __forceinline__ void undistort(const LensDistortion &D, float &xf, float &yf) {
+  const double xd = xf, yd = yf;
+  double x = xd, y = yd;
+  for (int it = 0; it < D.max_iterations; ++it) {
+    const double r = x * x + y * y;
+    const double d = 1.0 + r * (D.k1 + r * (D.k2 + r * (D.k3 + r * D.k4)));
+    const double fx = d * x + 2 * D.p1 * x * y + D.p2 * (r + 2 * x * x) - xd;
+    const double fy = d * y + 2 * D.p2 * x * y + D.p1 * (r + 2 * y * y) - yd;
+    const double d_r = D.k1 + r * (2.0 * D.k2 + r * (3.0 * D.k3 + r * 4.0 * D.k4));
+    const double d_x = 2.0 * x * d_r, d_y = 2.0 * y * d_r;
+    const double fx_x = d + d_x * x + 2.0 * D.p1 * y + 6.0 * D.p2 * x;
+    const double fx_y = d_y * x + 2.0 * D.p1 * x + 2.0 * D.p2 * y;
+    const double fy_x = d_x * y + 2.0 * D.p2 * y + 2.0 * D.p1 * x;
+    const double fy_y = d + d_y * y + 2.0 * D.p2 * x + 6.0 * D.p1 * y;
+    const double den = fy_x * fx_y - fx_x * fy_y;
+    if (fabs(den) > D.eps) {
+      x = x + (fx * fy_y - fy * fx_y) / den;
+      y = y + (fy * fx_x - fx * fy_x) / den;
+    }
+  }
+  xf = (float)x; yf = (float)y;
+}
 
 __device__ __forceinline__ void mat3_vec(const float *M, int ld, const float v[3], float out[3]) {
 #pragma unroll
@@ -38,6 +72,8 @@ __device__ __forceinline__ void to_ndc(const float o_in[3], const float d[3], co
   for (int i = 0; i < 3; ++i) d_ndc[i] = inf[i] - o_ndc[i];
 }
 
+/* kDistort = false: the pinhole camera; true: undistort the camera-space points first (distortion_params, :558-565) */
+template <bool kDistort>
 __global__ void pixels_to_rays_kernel(const RayGenArgs A) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= A.n) return;
@@ -50,6 +86,10 @@ __global__ void pixels_to_rays_kernel(const RayGenArgs A) {
     const float pd[3] = {x + (q == 1 ? 1.0f : 0.0f) + 0.5f, y + (q == 2 ? 1.0f : 0.0f) + 0.5f, 1.0f};
     float cam[3];
     mat3_vec(p2c, 3, pd, cam);
+    if constexpr (kDistort) {                         /* restacked with ones_like (:565) */
+      undistort(A.dist, cam[0], cam[1]);
+      cam[2] = 1.0f;
+    }
     cam[1] = -cam[1]; cam[2] = -cam[2];               /* OpenCV -> OpenGL */
     if (q == 0) { cam0[0] = cam[0]; cam0[1] = cam[1]; cam0[2] = cam[2]; }
     mat3_vec(c2w, 4, cam, dir[q]);

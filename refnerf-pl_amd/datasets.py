@@ -1,9 +1,10 @@
 """The random-ray training batcher in front of the hot path, on the device (second half).
 
 Mirrors `Dataset._next_train` / `Dataset._make_ray_batch` of the reference's internal/datasets.py (:395-485) for
-perspective cameras with `Config.cast_rays_in_train_step` semantics (configs.py:80): a batch is `batch_size //
-patch_size**2` random pixel patches drawn from all images ('all_images') or from one random image ('single_image');
-the colours are gathered and the rays cast (`camera_utils.cast_ray_batch` -> `refnerf_pixels_to_rays`) on the device, so
+perspective cameras (optionally with lens distortion) with `Config.cast_rays_in_train_step` semantics (configs.py:80): a
+batch is `batch_size // patch_size**2` random pixel patches drawn from all images ('all_images') or from one random image
+('single_image'); the colours are gathered and the rays cast (`camera_utils.cast_ray_batch` -> `refnerf_pixels_to_rays`,
+or `refnerf_pixels_to_rays_distorted` when the cameras carry a distortion dict) on the device, so
 a training step moves no per-ray data over PCIe.  Everything outside that (file loaders, pose normalisation, test / path
 cameras) stays out of scope.
 
@@ -20,8 +21,9 @@ from . import camera_utils, utils
 
 
 class TrainRayBatcher:
-    """images [n, H, W, C] (device or host, float), cameras = (pixtocams [n,3,3] | [3,3], camtoworlds [n,3,4], None,
-    pixtocam_ndc | None) -- the tuple `Dataset.cameras` holds in the reference."""
+    """images [n, H, W, C] (device or host, float), cameras = (pixtocams [n,3,3] | [3,3], camtoworlds [n,3,4],
+    distortion_params dict | None, pixtocam_ndc | None) -- the tuple `Dataset.cameras` holds in the reference
+    (datasets.py:607-621); the distortion dict is shared by all cameras and applied on the device."""
 
     def __init__(self, images, cameras: Sequence, near: float, far: float, batch_size: int, patch_size: int = 1,
                  batching: str = 'all_images', seed: int = 0, rank: int = 0, device: Optional[torch.device] = None,
@@ -33,10 +35,11 @@ class TrainRayBatcher:
         self.n_examples, self.height, self.width = self.images.shape[:3]
         pixtocams, camtoworlds, distortion, ndc = cameras
         if distortion is not None:
-            raise ValueError('lens distortion is outside the device ray generator')
+            camera_utils.lens_distortion(distortion)       # unknown keys raise TypeError here, not at the first batch
+            distortion = dict(distortion)
         f32 = dict(dtype=torch.float32, device=self.device)
         self.cameras = (torch.as_tensor(np.asarray(pixtocams), **f32), torch.as_tensor(np.asarray(camtoworlds), **f32)[..., :3, :4],
-                        None, None if ndc is None else torch.as_tensor(np.asarray(ndc), **f32))
+                        distortion, None if ndc is None else torch.as_tensor(np.asarray(ndc), **f32))
         self.near, self.far = float(near), float(far)
         self.batch_size, self.patch_size, self.batching, self.debug_mode = int(batch_size), int(patch_size), batching, debug_mode
         self.gen = torch.Generator(device=self.device)
