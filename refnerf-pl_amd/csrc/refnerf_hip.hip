@@ -41,6 +41,57 @@ namespace rn {
 /* ------------------------------------------------------------------ */
 
 
+/* element e of an fp32 A image -> (k-step, row block, lane): [step][lane][ob], eight-block ops [step][q][lane][4] with ob = 4 q + e % 4 */
+__device__ __forceinline__ void a_decode(int e, int stride, int &step, int &ob, int &lane) {
+  step = e / (stride * 64);
+  if (stride == 8) { const int rem = e % 512; ob = (rem >> 8) * 4 + (rem & 3); lane = (rem & 255) >> 2; }
+  else { ob = e % stride; lane = (e / stride) % 64; }
+}
+
+/* ---- the 16-bit images of the chain GEMMs: [k-step][ob][lane][8], element e of lane (h = lane / 32, n = lane % 32) ---- */
+/* accumulator row that feeds slot (h, e) of 16-wide k-step st */
+__device__ __forceinline__ int kslot16(int st, int h, int e) {
+  const int r = 8 * (st & 1) + e;
+  return 32 * (st >> 1) + (r & 3) + 8 * (r >> 2) + 4 * h;
+}
+/* transposed op t (refnerf_layout.h: bt_off / ht_off): W[o = k slot][in_row = 32 ob + n] */
+__device__ __forceinline__ float top16_value(const float *__restrict__ P, int t, int st, int ob, int lane, int e) {
+  const Op o = PACKED.top[t];
+  const int h = lane >> 5, in_row = ob * 32 + (lane & 31);
+  if (ob >= o.nob) return 0.0f;
+  if (t == TOP_HEADS) {
+    const int hr = 16 * st + 8 * h + e;                      /* head row feeding this k slot */
+    return (hr < HROWS) ? canon_w(P, OP_HEADS, hr, in_row) : 0.0f;
+  }
+  const TopSrc src = PACKED.top_src[t];
+  const int n_rows = (o.nob == 8) ? WIDTH : (o.nob == 3 ? IPE_DIM : DIR_IN);   /* rows beyond are padding */
+  return (in_row < n_rows) ? canon_w(P, src.fwd_op, kslot16(st, h, e), src.col0 + in_row) : 0.0f;
+}
+/* forward op fo (bf_off / hf_off): W[row = 32 ob + n][k], register steps in k-slot order, then the LDS steps in plain order */
+__device__ __forceinline__ float fwd16_value(const float *__restrict__ P, int fo, int st, int ob, int lane, int e) {
+  const int rst = bf_reg_steps(fo);
+  const int h = lane >> 5, row = ob * 32 + (lane & 31);
+  if (ob >= PACKED.op[fo].nob) return 0.0f;
+  if (st < rst) return canon_w(P, fo, row, kslot16(st, h, e));
+  const int kl = 16 * (st - rst) + 8 * h + e;
+  const int valid_k = (fo == 0 || fo == 5) ? IPE_DIM : DIR_IN;
+  return (kl < valid_k) ? canon_w(P, fo, row, (rst ? WIDTH : 0) + kl) : 0.0f;
+}
+/* the two stores: bf16, or the split-f16 pair -- per k-step [hi | lo], the v - hi residual 4096 halves behind its hi half */
+__device__ __forceinline__ void store16(__bf16 *dst, int idx, float v) { dst[idx] = (__bf16)v; }
+__device__ __forceinline__ void store16(_Float16 *dst, int idx, float v) {
+  const _Float16 hi = (_Float16)v;
+  const size_t base = (size_t)(idx >> 12) * (2 * 4096) + (idx & 4095);
+  dst[base] = hi;
+  dst[base + 4096] = (_Float16)(v - (float)hi);
+}
+/* one image of `steps` k-steps, value(st, ob, lane, e), by the whole x-grid */
+template <typename E, typename F>
+__device__ __forceinline__ void pack_image16(E *dst, int steps, F &&value) {
+  for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < steps * 4096; idx += gridDim.x * blockDim.x)
+    store16(dst, idx, value(idx >> 12, (idx >> 9) & 7, (idx >> 3) & 63, idx & 7));
+}
+
 __global__ void pack_weights_f32(const float *__restrict__ P, float *__restrict__ out) {
   int op = blockIdx.y;
   if (op < NUM_OPS) {
@@ -49,9 +100,8 @@ __global__ void pack_weights_f32(const float *__restrict__ P, float *__restrict_
     int n_b = o.nob * 32;
     for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < n_a + n_b; e += gridDim.x * blockDim.x) {
       if (e < n_a) {
-        int ob, lane, step = e / (o.stride * 64);
-        if (o.stride == 8) { const int rem = e % 512; ob = (rem >> 8) * 4 + (rem & 3); lane = (rem & 255) >> 2; }   /* [step][q][lane][4] */
-        else { ob = e % o.stride; lane = (e / o.stride) % 64; }
+        int step, ob, lane;
+        a_decode(e, o.stride, step, ob, lane);
         int h = lane >> 5, row = ob * 32 + (lane & 31);
         float v = 0.0f;
         if (ob < o.nob) {
@@ -81,9 +131,8 @@ __global__ void pack_weights_f32(const float *__restrict__ P, float *__restrict_
     const TopSrc src = PACKED.top_src[t];
     int n_a = (o.reg_steps + o.lds_steps) * 64 * o.stride;
     for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < n_a; e += gridDim.x * blockDim.x) {
-      int ob, lane, step = e / (o.stride * 64);
-        if (o.stride == 8) { const int rem = e % 512; ob = (rem >> 8) * 4 + (rem & 3); lane = (rem & 255) >> 2; }   /* [step][q][lane][4] */
-        else { ob = e % o.stride; lane = (e / o.stride) % 64; }
+      int step, ob, lane;
+      a_decode(e, o.stride, step, ob, lane);
       int h = lane >> 5, in_row = ob * 32 + (lane & 31);
       float v = 0.0f;
       if (ob < o.nob) {
@@ -98,103 +147,22 @@ __global__ void pack_weights_f32(const float *__restrict__ P, float *__restrict_
       }
       out[o.a_off + e] = v;
     }
-  } else if (op < NUM_OPS + 2 * NUM_TOPS) {
-    /* bf16 transposed ops of the bf16-chain backward (refnerf_layout.h: bt_off) */
-    const int t = op - NUM_OPS - NUM_TOPS;
-    const Op o = PACKED.top[t];
-    const TopSrc src = PACKED.top_src[t];
-    const int steps = (t == TOP_HEADS) ? BT_HEADS_STEPS : BT_CHAIN_STEPS;
-    __bf16 *dst = reinterpret_cast<__bf16 *>(out + PACKED.bt_off[t]);
-    for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < steps * 64 * 8 * 8; idx += gridDim.x * blockDim.x) {
-      const int e = idx & 7, lane = (idx >> 3) & 63, ob = (idx >> 9) & 7, st = idx >> 12;   /* [step][ob][lane][8] */
-      const int h = lane >> 5, in_row = ob * 32 + (lane & 31);
-      float v = 0.0f;
-      if (ob < o.nob) {
-        if (t == TOP_HEADS) {
-          const int hr = 16 * st + 8 * h + e;
-          v = (hr < HROWS) ? canon_w(P, OP_HEADS, hr, in_row) : 0.0f;
-        } else {
-          const int r = 8 * (st & 1) + e;
-          const int oo = 32 * (st >> 1) + (r & 3) + 8 * (r >> 2) + 4 * h;
-          const int n_rows = (o.nob == 8) ? WIDTH : (o.nob == 3 ? IPE_DIM : DIR_IN);   /* rows beyond are padding */
-          v = (in_row < n_rows) ? canon_w(P, src.fwd_op, oo, src.col0 + in_row) : 0.0f;
-        }
-      }
-      dst[idx] = (__bf16)v;
-    }
-  } else if (op < 2 * NUM_OPS + 2 * NUM_TOPS) {
-    /* bf16 forward ops of the bf16-chain training forward (refnerf_layout.h: bf_off) */
-    const int fo = op - NUM_OPS - 2 * NUM_TOPS;
-    const Op o = PACKED.op[fo];
-    const int rst = bf_reg_steps(fo), steps = rst + bf_lds_steps(fo);
-    const int valid_k = (fo == 0 || fo == 5) ? IPE_DIM : DIR_IN;
-    __bf16 *dst = reinterpret_cast<__bf16 *>(out + PACKED.bf_off[fo]);
-    for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < steps * 64 * 8 * 8; idx += gridDim.x * blockDim.x) {
-      const int e = idx & 7, lane = (idx >> 3) & 63, ob = (idx >> 9) & 7, st = idx >> 12;   /* [step][ob][lane][8] */
-      const int h = lane >> 5, row = ob * 32 + (lane & 31);
-      float v = 0.0f;
-      if (ob < o.nob) {
-        if (st < rst) {
-          const int r = 8 * (st & 1) + e;
-          v = canon_w(P, fo, row, 32 * (st >> 1) + (r & 3) + 8 * (r >> 2) + 4 * h);
-        } else {
-          const int kl = 16 * (st - rst) + 8 * h + e;
-          v = (kl < valid_k) ? canon_w(P, fo, row, (rst ? WIDTH : 0) + kl) : 0.0f;
-        }
-      }
-      dst[idx] = (__bf16)v;
-    }
-  } else if (op < 2 * NUM_OPS + 3 * NUM_TOPS) {
-    /* split-f16 transposed ops (refnerf_layout.h: ht_off): the bt_off values as hi + lo halves, [k-step][hi | lo][ob][lane][8] */
-    const int t = op - 2 * NUM_OPS - 2 * NUM_TOPS;
-    const Op o = PACKED.top[t];
-    const TopSrc src = PACKED.top_src[t];
-    const int steps = (t == TOP_HEADS) ? BT_HEADS_STEPS : BT_CHAIN_STEPS;
-    _Float16 *dst = reinterpret_cast<_Float16 *>(out + PACKED.ht_off[t]);
-    for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < steps * 64 * 8 * 8; idx += gridDim.x * blockDim.x) {
-      const int e = idx & 7, lane = (idx >> 3) & 63, ob = (idx >> 9) & 7, st = idx >> 12;
-      const int h = lane >> 5, in_row = ob * 32 + (lane & 31);
-      float v = 0.0f;
-      if (ob < o.nob) {
-        if (t == TOP_HEADS) {
-          const int hr = 16 * st + 8 * h + e;
-          v = (hr < HROWS) ? canon_w(P, OP_HEADS, hr, in_row) : 0.0f;
-        } else {
-          const int r = 8 * (st & 1) + e;
-          const int oo = 32 * (st >> 1) + (r & 3) + 8 * (r >> 2) + 4 * h;
-          const int n_rows = (o.nob == 8) ? WIDTH : (o.nob == 3 ? IPE_DIM : DIR_IN);
-          v = (in_row < n_rows) ? canon_w(P, src.fwd_op, oo, src.col0 + in_row) : 0.0f;
-        }
-      }
-      const _Float16 hi = (_Float16)v;
-      const size_t base = (size_t)st * (2 * 64 * 8 * 8) + (idx & 4095);
-      dst[base] = hi;
-      dst[base + 4096] = (_Float16)(v - (float)hi);
-    }
   } else if (op < 3 * NUM_OPS + 3 * NUM_TOPS) {
-    /* split-f16 forward ops (refnerf_layout.h: hf_off) */
-    const int fo = op - 2 * NUM_OPS - 3 * NUM_TOPS;
-    const Op o = PACKED.op[fo];
-    const int rst = bf_reg_steps(fo), steps = rst + bf_lds_steps(fo);
-    const int valid_k = (fo == 0 || fo == 5) ? IPE_DIM : DIR_IN;
-    _Float16 *dst = reinterpret_cast<_Float16 *>(out + PACKED.hf_off[fo]);
-    for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < steps * 64 * 8 * 8; idx += gridDim.x * blockDim.x) {
-      const int e = idx & 7, lane = (idx >> 3) & 63, ob = (idx >> 9) & 7, st = idx >> 12;
-      const int h = lane >> 5, row = ob * 32 + (lane & 31);
-      float v = 0.0f;
-      if (ob < o.nob) {
-        if (st < rst) {
-          const int r = 8 * (st & 1) + e;
-          v = canon_w(P, fo, row, 32 * (st >> 1) + (r & 3) + 8 * (r >> 2) + 4 * h);
-        } else {
-          const int kl = 16 * (st - rst) + 8 * h + e;
-          v = (kl < valid_k) ? canon_w(P, fo, row, (rst ? WIDTH : 0) + kl) : 0.0f;
-        }
-      }
-      const _Float16 hi = (_Float16)v;
-      const size_t base = (size_t)st * (2 * 64 * 8 * 8) + (idx & 4095);
-      dst[base] = hi;
-      dst[base + 4096] = (_Float16)(v - (float)hi);
+    /* the 16-bit images, in blob order: bf16 transposed (bt_off: the bf16-chain backward), bf16 forward (bf_off: the bf16-chain
+     * training forward), split-f16 transposed (ht_off), split-f16 forward (hf_off) */
+    const int j = op - NUM_OPS - NUM_TOPS, half = NUM_TOPS + NUM_OPS;
+    const bool split = j >= half;
+    const int i = split ? j - half : j;                     /* transposed op i, or forward op i - NUM_TOPS */
+    if (i < NUM_TOPS) {
+      const int t = i, steps = (t == TOP_HEADS) ? BT_HEADS_STEPS : BT_CHAIN_STEPS;
+      auto value = [&](int st, int ob, int lane, int e) { return top16_value(P, t, st, ob, lane, e); };
+      if (split) pack_image16(reinterpret_cast<_Float16 *>(out + PACKED.ht_off[t]), steps, value);
+      else pack_image16(reinterpret_cast<__bf16 *>(out + PACKED.bt_off[t]), steps, value);
+    } else {
+      const int fo = i - NUM_TOPS, steps = bf_reg_steps(fo) + bf_lds_steps(fo);
+      auto value = [&](int st, int ob, int lane, int e) { return fwd16_value(P, fo, st, ob, lane, e); };
+      if (split) pack_image16(reinterpret_cast<_Float16 *>(out + PACKED.hf_off[fo]), steps, value);
+      else pack_image16(reinterpret_cast<__bf16 *>(out + PACKED.bf_off[fo]), steps, value);
     }
   } else {
     /* WD / WRGB: raw_density.weight and rgb_layer.weight rows in accumulator layout [ob][h][16] */
@@ -237,29 +205,15 @@ __global__ void pack_weights_ext(const float *__restrict__ P, const float *__res
       dst[e] = (live && ob < 3) ? W[oo * EXT_K + in_row] : 0.0f;
     }
   } else {
-    /* split copies: element idx = [step][ob][lane][e] of a 4096-half plane pair (hi plane, lo plane 4096 halves behind) */
+    /* split copies: the [k-step][hi | lo][ob][lane][8] layout of ht_off / hf_off */
     const bool fwd = kind == 2;
-    const int steps = fwd ? BF_IPE_STEPS : BT_CHAIN_STEPS;
     _Float16 *dst = reinterpret_cast<_Float16 *>(out + (fwd ? pext_hf_off(L, g) : pext_ht_off(L, g)));
-    for (int i = e0; i < steps * 4096; i += stride) {
-      const int e = i & 7, lane = (i >> 3) & 63, ob = (i >> 9) & 7, st = i >> 12;
+    pack_image16(dst, fwd ? BF_IPE_STEPS : BT_CHAIN_STEPS, [&](int st, int ob, int lane, int e) {
       const int h = lane >> 5, r32 = ob * 32 + (lane & 31);
-      float v = 0.0f;
-      if (live) {
-        if (fwd) {
-          const int kl = 16 * st + 8 * h + e;                     /* plain order over the fp32 X tile (bf_off's LDS steps) */
-          v = W[r32 * EXT_K + kl];
-        } else if (ob < 3) {
-          const int r = 8 * (st & 1) + e;
-          const int oo = 32 * (st >> 1) + (r & 3) + 8 * (r >> 2) + 4 * h;
-          v = W[oo * EXT_K + r32];
-        }
-      }
-      const _Float16 hi = (_Float16)v;
-      const size_t base = (size_t)st * (2 * 4096) + (i & 4095);
-      dst[base] = hi;
-      dst[base + 4096] = (_Float16)(v - (float)hi);
-    }
+      if (!live) return 0.0f;
+      if (fwd) return W[r32 * EXT_K + 16 * st + 8 * h + e];   /* plain order over the fp32 X tile (bf_off's LDS steps) */
+      return ob < 3 ? W[kslot16(st, h, e) * EXT_K + r32] : 0.0f;
+    });
   }
 }
 
@@ -709,15 +663,13 @@ namespace {
 struct BwdPlan { long long S, pitch; int slices, k_per_slice; size_t act_bytes, delta_off, part_off, seed_off, cmin_off, total, act_ext_off, part_ext_off; };
 /* groups > 1 (general IPE basis): the tail matrix of the groups' IPE features behind ACT, the tail's split-K partials behind the seeds */
 /* split-K slices of the weight-gradient GEMMs (one PART image of NUM_PARAMS floats each, reduced in a fixed order) */
-#ifndef REFNERF_MAX_SLICES
-#define REFNERF_MAX_SLICES 32
-#endif
+constexpr int MAX_SLICES = 32;
 BwdPlan bwd_plan(int R, int N, int groups = 0) {
   BwdPlan p;
   p.S = (long long)R * N;
   p.pitch = (p.S + 127) / 128 * 128;
   long long sl = (p.S + 2047) / 2048;
-  p.slices = (int)(sl < 1 ? 1 : (sl > REFNERF_MAX_SLICES ? REFNERF_MAX_SLICES : sl));
+  p.slices = (int)(sl < 1 ? 1 : (sl > MAX_SLICES ? MAX_SLICES : sl));
   long long per = (p.S + p.slices - 1) / p.slices;
   p.k_per_slice = (int)((per + rn::WG_KT - 1) / rn::WG_KT * rn::WG_KT);
   p.act_bytes = sizeof(float) * (size_t)rn::ACT_ALLOC_ROWS * p.pitch;
@@ -1087,7 +1039,7 @@ int refnerf_level_backward(const void *d_packed, const refnerf_level_cfg *cfg, c
   a.delta = (float *)(ws + plan.delta_off);
   a.seeds = (float *)(ws + plan.seed_off);
   a.pitch = plan.pitch;
-  const bool act16 = saved->activations_format == REFNERF_ACT_BF16, del16 = cfg->precision == REFNERF_PREC_BF16 && (REFNERF_DELTA16 != 0);
+  const bool act16 = saved->activations_format == REFNERF_ACT_BF16, del16 = cfg->precision == REFNERF_PREC_BF16;
   const bool sq = saved->activations_format == REFNERF_ACT_SQ;
   if (saved->activations_format != REFNERF_ACT_F32 && saved->activations_format != REFNERF_ACT_BF16 && !sq)
     return fail(REFNERF_EINVAL, "refnerf_level_backward: unknown activations_format%s");

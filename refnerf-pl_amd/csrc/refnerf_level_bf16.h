@@ -59,26 +59,17 @@ __device__ __forceinline__ unsigned cvt_pk_mm(float lo, float hi) {
   typename MM::v2 r = __builtin_convertvector((v2f){lo, hi}, typename MM::v2);
   return __builtin_bit_cast(unsigned, r);
 }
-#ifdef REFNERF_EVAL_EXACT_ENC
-constexpr bool ENC_FAST = false;     /* experiment: libm-accurate encodings / head activations in this kernel */
-#else
-constexpr bool ENC_FAST = true;
-#endif
+constexpr bool ENC_FAST = true;      /* fast encodings / head activations in the plain 16-bit kernels (the split kernel uses the exact ones) */
 
 constexpr int BT = 256;                               /* samples per pass: 8 waves x 32 */
 constexpr int BF_NW = 8;                              /* waves per workgroup */
 constexpr int BF_NTHREADS = 64 * BF_NW;
-/* REFNERF_RING_SLOTS = 4 (round 6): a fourth ring slot = TWO chunk-times between the issue of a chunk's LDS-DMA and the rendezvous
- * that certifies it (the 3-slot ring gives one) */
-#ifndef REFNERF_RING_SLOTS
-#define REFNERF_RING_SLOTS 3
-#endif
-constexpr int BF_RING_BYTES = REFNERF_RING_SLOTS * BF_CHUNK_BYTES;     /* 51 KB (68 KB with four slots) */
+/* three slots: one chunk-time between the issue of a chunk's LDS-DMA and the rendezvous that certifies it (a fourth slot, two
+ * chunk-times, was tried in round 6 and not adopted: docs/EXPERIMENTS.md) */
+constexpr int BF_RING_SLOTS = 3;
+constexpr int BF_RING_BYTES = BF_RING_SLOTS * BF_CHUNK_BYTES;     /* 51 KB */
 constexpr int BF_X_BYTES = (IPE_DIM / 8) * BT * 16;   /* 12 k-groups x 256 x 16 B = 48 KB */
-#ifndef REFNERF_BF_AF
-#define REFNERF_BF_AF 2
-#endif
-constexpr int AF = REFNERF_BF_AF;                     /* A-fragment ring depth (k-steps ahead) */
+constexpr int AF = 2;                                 /* A-fragment ring depth (k-steps ahead) */
 static_assert(AF == 1 || AF == 2 || AF == 4, "the ring index k % AF must stay in phase across 8- and 16-step chunks, and the ring may only run into "
                                              "the next chunk after that chunk's rendezvous (8-step chunks: k >= 4)");
 /* measured in the full kernel (C2, round 2): AF = 2 runs 1.2 % faster than 4 (4 fewer fragment registers: 36 instead of
@@ -95,66 +86,48 @@ struct Pipe {
   const char *xps;   /* split mode: this lane's B fragment in the IPE planes of a run (hi plane; the lo plane (BT / 2) * 16 bytes behind) */
   int seq;           /* split mode: chunks issued so far in this pass (the spatial section is streamed twice) */
   int cur_off, nxt_off, fil_off;   /* ring slots: being consumed / landed next / free */
-  int nx2_off;                     /* four-slot ring: the chunk behind `nxt` (in flight or landed) */
   int dma_left;      /* chunks still to be DMA'd by this workgroup */
   int lane, wave, h;
-  long long t_vm, t_bar;   /* debug (REFNERF_PROF): cycles spent in the DMA wait / in the barrier */
+  long long t_vm, t_bar;   /* debug (-DREFNERF_PROF_WAITS): cycles spent in the DMA wait / in the barrier */
 };
 
+/* The rendezvous of a chunk: this wave's DMA pieces have landed, then every wave's.  __syncthreads() is a workgroup fence +
+ * barrier; a bare s_barrier (without the fence's lgkmcnt(0) drain of the A-fragment reads issued ahead) measured the same.
+ * -DREFNERF_PROF_WAITS: the cycles of the DMA wait and of the barrier accumulate in the Pipe. */
+#ifdef REFNERF_PROF_WAITS
+#define RN_RENDEZVOUS(p) do { \
+    long long t0_ = (long long)__builtin_readcyclecounter(); \
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); \
+    long long t1_ = (long long)__builtin_readcyclecounter(); \
+    __syncthreads(); \
+    (p).t_vm += t1_ - t0_; \
+    (p).t_bar += (long long)__builtin_readcyclecounter() - t1_; } while (0)
+#else
+#define RN_RENDEZVOUS(p) do { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); __syncthreads(); } while (0)
+#endif
+__device__ __forceinline__ void ring_rotate(Pipe &p) {
+  const int t = p.cur_off;
+  p.cur_off = p.nxt_off;
+  p.nxt_off = p.fil_off;
+  p.fil_off = t;
+}
 /* LDS-DMA of one 17 KB chunk into the ring slot at `slot_off`.  Wave w moves the
  * adjacent pieces 3w..3w+2 (waves 0-4; wave 5 moves 15,16): one address and the
  * instruction's immediate offset cover both the global and the LDS side.
  * (Measured alternatives: all pieces issued by the prioritised waves 4-7, or
  * 2 pieces per wave with 16 KB chunks -- both slower in the full kernel.) */
-/* REFNERF_BF_SPREAD: the (up to) three pieces a wave moves per chunk are issued one at a time, two k-steps apart, instead of
- * back to back right behind the rendezvous (an LDS-DMA piece costs its wave 100-185 issue cycles inside a burst, ~60 among
- * MFMAs: MI355X_MICROARCH.md); `piece` = 0, 1, 2, or -1 for all three.  Measured (round 4, C2, same box): f16x2 4.865 -> 4.839 ms
- * per step, bf16 2.105 -> 2.086, f16 2.175 -> 2.153, results bit-identical: on. */
-#ifndef REFNERF_BF_SPREAD
-#define REFNERF_BF_SPREAD 1
-#endif
-#ifndef REFNERF_DMA_AUX
-#define REFNERF_DMA_AUX 0   /* cache policy bits of the weight stream's LDS-DMA */
-#endif
-/* the rendezvous of a chunk: this wave's DMA pieces have landed, then every wave's.  REFNERF_BARE_BARRIER: s_barrier alone behind
- * the wait -- __syncthreads() is a workgroup fence + barrier, and the fence is `s_waitcnt vmcnt(0) lgkmcnt(0)`: it also drains
- * the A-fragment reads that were issued ahead for the MFMAs BEHIND the rendezvous */
-#ifndef REFNERF_BARE_BARRIER
-#define REFNERF_BARE_BARRIER 0
-#endif
-#if REFNERF_RING_SLOTS == 4
-/* four slots: chunk c + 1 must have landed, chunk c + 2 (<= 3 pieces per wave, wave 5: 2) may still fly: vmcnt(2) certifies c + 1 for
- * every wave (loads return in order).  No __syncthreads(): its fence is vmcnt(0); wavefront-scope fences keep the allocator sane. */
-#define RN_RENDEZVOUS() do { asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); \
-    __builtin_amdgcn_s_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); } while (0)
-#elif REFNERF_BARE_BARRIER
-/* (round 6) the wavefront-scope fences emit no instruction, but without them the register allocator spills 129-154 VGPRs in
- * these kernels: round 5's "bare barrier is 11 % slower" was that spill.  Measured with the fences (0 spills): f16x2 3.86 ->
- * 3.86 ms per C2 step, bf16 2.077 -> 2.067: the lgkmcnt(0) drain of __syncthreads()' fence costs nothing here; it stays. */
-#define RN_RENDEZVOUS() do { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); \
-    __builtin_amdgcn_s_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); } while (0)
-#else
-#define RN_RENDEZVOUS() do { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); __syncthreads(); } while (0)
-#endif
-__device__ __forceinline__ void ring_rotate(Pipe &p) {
-  const int t = p.cur_off;
-  p.cur_off = p.nxt_off;
-#if REFNERF_RING_SLOTS == 4
-  p.nxt_off = p.nx2_off;
-  p.nx2_off = p.fil_off;
-#else
-  p.nxt_off = p.fil_off;
-#endif
-  p.fil_off = t;
-}
+/* The (up to) three pieces a wave moves per chunk are issued one at a time, two k-steps apart, instead of back to back right
+ * behind the rendezvous (an LDS-DMA piece costs its wave 100-185 issue cycles inside a burst, ~60 among MFMAs:
+ * MI355X_MICROARCH.md); `piece` = 0, 1, 2, or -1 for all three.  Measured (round 4): f16x2 4.865 -> 4.839 ms per step,
+ * bf16 2.105 -> 2.086, results bit-identical.  The DMA keeps the default cache policy (aux 0: `nt` measured +14 %, `sc1` nothing). */
 template <bool SPLIT = false>
 __device__ __forceinline__ void issue_chunk(Pipe &p, int slot_off, int piece = -1) {
   if (p.dma_left > 0) {
     if (p.wave < 6) {
       lptr_t dst = (lptr_t)(p.wbuf + slot_off + p.wave * 3072);
-      if (piece < 0 || piece == 0) __builtin_amdgcn_global_load_lds((gptr_t)p.src, dst, 16, 0, REFNERF_DMA_AUX);
-      if (piece < 0 || piece == 1) __builtin_amdgcn_global_load_lds((gptr_t)p.src, dst, 16, 1024, REFNERF_DMA_AUX);
-      if ((piece < 0 || piece == 2) && p.wave < 5) __builtin_amdgcn_global_load_lds((gptr_t)p.src, dst, 16, 2048, REFNERF_DMA_AUX);
+      if (piece < 0 || piece == 0) __builtin_amdgcn_global_load_lds((gptr_t)p.src, dst, 16, 0, 0);
+      if (piece < 0 || piece == 1) __builtin_amdgcn_global_load_lds((gptr_t)p.src, dst, 16, 1024, 0);
+      if ((piece < 0 || piece == 2) && p.wave < 5) __builtin_amdgcn_global_load_lds((gptr_t)p.src, dst, 16, 2048, 0);
     }
     if (piece >= 0 && piece < 2) return;             /* the stream position moves on with the last piece */
     p.src += BF_CHUNK_BYTES;
@@ -225,6 +198,7 @@ __device__ __forceinline__ void bf_chunk(Pipe &p, typename MM::v8 (&a)[AF], cons
   typedef typename MM::v8 v8mm;
   constexpr int KS = (KIND == BF_LDS8) ? 8 : 16;
   constexpr int L0 = (KIND == BF_BNLDS) ? 8 : 0;      /* first LDS step (for the LDS kinds) */
+  constexpr int RDV = KS / 2 - 1;
   static_assert(KS % AF == 0, "ring phase");
   const char *w = p.wbuf + p.cur_off;
   const char *cur = w + 1024 + p.lane * 16;
@@ -248,28 +222,13 @@ __device__ __forceinline__ void bf_chunk(Pipe &p, typename MM::v8 (&a)[AF], cons
       const int kl2 = k + 2 - L0;                       /* LDS step to fetch now */
       if (kl2 >= 0 && kl2 < 8 && !(KIND == BF_LDS8 && kl2 < 2)) xr[kl2 & 1] = lds_b<MM, REAL_L>(p, kl2);
     }
-#ifndef REFNERF_BF_RDV
-#define REFNERF_BF_RDV (KS / 2 - 1)
-#endif
-    if (k == REFNERF_BF_RDV) {
+    if (k == RDV) {
       /* mid-chunk rendezvous: chunk c+1 is complete for every wave, chunk c-1's slot is free */
-#ifdef REFNERF_PROF_WAITS
-      long long t0 = (long long)__builtin_readcyclecounter();
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      long long t1 = (long long)__builtin_readcyclecounter();
-      __syncthreads();
-      long long t2 = (long long)__builtin_readcyclecounter();
-      p.t_vm += t1 - t0;
-      p.t_bar += t2 - t1;
-#else
-      RN_RENDEZVOUS();
-#endif
-      issue_chunk<SPLIT>(p, p.fil_off, REFNERF_BF_SPREAD ? 0 : -1);
+      RN_RENDEZVOUS(p);
+      issue_chunk<SPLIT>(p, p.fil_off, 0);
     }
-    if (REFNERF_BF_SPREAD) {
-      if (k == REFNERF_BF_RDV + 2) issue_chunk<SPLIT>(p, p.fil_off, 1);
-      if (k == REFNERF_BF_RDV + 4) issue_chunk<SPLIT>(p, p.fil_off, 2);
-    }
+    if (k == RDV + 2) issue_chunk<SPLIT>(p, p.fil_off, 1);
+    if (k == RDV + 4) issue_chunk<SPLIT>(p, p.fil_off, 2);
     __builtin_amdgcn_sched_barrier(0);
   }
   ring_rotate(p);
@@ -283,7 +242,7 @@ template <bool SPLIT = false>
 __device__ __forceinline__ void idle_pass(Pipe &p) {
 #pragma unroll 1
   for (int c = 0; c < (SPLIT ? SPPACKED.chunks_per_pass : BFPACKED.chunks_per_pass); ++c) {
-    RN_RENDEZVOUS();
+    RN_RENDEZVOUS(p);
     issue_chunk<SPLIT>(p, p.fil_off);
     ring_rotate(p);
   }
@@ -361,16 +320,13 @@ __device__ __forceinline__ void level_fwd_mm(const LevelArgs &A) {
   p.src_end = p.src + (size_t)BFPACKED.chunks_per_pass * BF_CHUNK_BYTES;
   p.wbuf = WB;
   p.xp = Xb + (h * BT + col) * 16;
-  p.cur_off = 0; p.nxt_off = BF_CHUNK_BYTES; p.nx2_off = 2 * BF_CHUNK_BYTES; p.fil_off = (REFNERF_RING_SLOTS - 1) * BF_CHUNK_BYTES;
+  p.cur_off = 0; p.nxt_off = BF_CHUNK_BYTES; p.fil_off = 2 * BF_CHUNK_BYTES;
   p.dma_left = n_pass * BFPACKED.chunks_per_pass;
   p.lane = lane; p.wave = wave; p.h = h;
   p.t_vm = 0; p.t_bar = 0;
   RN_STAMPW(A, 0);
   issue_chunk(p, p.cur_off);                                 /* overlaps with the resampler */
   issue_chunk(p, p.nxt_off);
-#if REFNERF_RING_SLOTS == 4
-  issue_chunk(p, p.nx2_off);
-#endif
 
   resample_phase<BF_NW, false>(A, reinterpret_cast<float *>(Xb), TD, NRM, ray0, wave, lane);   /* P0 */
   RN_STAMPW(A, 1);
@@ -380,9 +336,7 @@ __device__ __forceinline__ void level_fwd_mm(const LevelArgs &A) {
 
   /* static priority for the younger wave of each SIMD (waves 4-7): age-based
    * arbitration otherwise lets waves 0-3 run ahead and idle at every rendezvous */
-#ifndef REFNERF_BF_NOPRIO
   if (wave >= BF_NW / 2) __builtin_amdgcn_s_setprio(1);
-#endif
   v4uu R0[16], R1[16], bn[8];
   v8mm ar[AF];
 #pragma unroll
@@ -636,13 +590,10 @@ template <int KIND> constexpr int sq_release(int j) {
 }
 /* One chunk.  `fr` = the piece ring: on entry pieces 0..3 of this chunk, on exit those of the next one.  `in`: the layer input
  * as [H(s) L(s)] x 8 k-steps (SQ_X: from the LDS planes instead).  hook(j): caller's VALU work behind MFMA j. */
-/* REFNERF_SQ_PREBIAS: a chunk that opens a slice finds its bias already in `acc` -- fetched by the chunk before it (PRE: this
- * chunk fetches the bias piece of the NEXT chunk into `nacc` right behind its rendezvous) -- instead of loading it and waiting
- * a full LDS round trip in front of its first MFMA */
-#ifndef REFNERF_SQ_PREBIAS
-#define REFNERF_SQ_PREBIAS 1
-#endif
-template <int KIND, bool FIRST, bool PRE, typename Hook = NoHook>
+/* A chunk that opens a slice finds its bias already in `acc` -- fetched by the chunk before it (PRE: this chunk fetches the
+ * bias piece of the NEXT chunk into `nacc` right behind its rendezvous) -- instead of loading it and waiting a full LDS round
+ * trip in front of its first MFMA */
+template <int KIND, bool PRE, typename Hook = NoHook>
 __device__ __forceinline__ void sq_chunk(Pipe &p, sq_v8 (&fr)[SQ_NF], const v4uu (&in)[16], SqAcc &acc, SqAcc &nacc, Hook &&hook = Hook()) {
   constexpr int NM = sq_nm<KIND>(), NP = sq_np<KIND>();
   constexpr int RDV = NM / 2 - 1;
@@ -651,11 +602,6 @@ __device__ __forceinline__ void sq_chunk(Pipe &p, sq_v8 (&fr)[SQ_NF], const v4uu
   const char *nxt = p.wbuf + p.nxt_off + 1024 + p.lane * 16;
   sq_v8 xb[2];
   if (KIND == SQ_X) { xb[0] = lds_frag<MmF16>(p.xps); xb[1] = lds_frag<MmF16>(p.xps + (BT / 2) * 16); }
-  if (FIRST && !REFNERF_SQ_PREBIAS) {
-    const v4f *bp = reinterpret_cast<const v4f *>(w + (p.lane >> 4) * 16);      /* bias piece [T][b][4] */
-    acc.t0 = bp[0];
-    acc.t1 = bp[4];
-  }
   __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
   for (int j = 0; j < NM; ++j) {
@@ -678,28 +624,16 @@ __device__ __forceinline__ void sq_chunk(Pipe &p, sq_v8 (&fr)[SQ_NF], const v4uu
     }
     if (j == RDV) {
       /* mid-chunk rendezvous: chunk c+1 is complete for every wave, chunk c-1's slot is free */
-#ifdef REFNERF_PROF_WAITS
-      long long t0 = (long long)__builtin_readcyclecounter();
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      long long t1 = (long long)__builtin_readcyclecounter();
-      __syncthreads();
-      long long t2 = (long long)__builtin_readcyclecounter();
-      p.t_vm += t1 - t0;
-      p.t_bar += t2 - t1;
-#else
-      RN_RENDEZVOUS();
-#endif
-      issue_chunk<true>(p, p.fil_off, REFNERF_BF_SPREAD ? 0 : -1);
-      if (PRE && REFNERF_SQ_PREBIAS) {
+      RN_RENDEZVOUS(p);
+      issue_chunk<true>(p, p.fil_off, 0);
+      if (PRE) {
         const v4f *bp = reinterpret_cast<const v4f *>(p.wbuf + p.nxt_off + (p.lane >> 4) * 16);
         nacc.t0 = bp[0];
         nacc.t1 = bp[4];
       }
     }
-    if (REFNERF_BF_SPREAD) {
-      if (j == RDV + 4) issue_chunk<true>(p, p.fil_off, 1);
-      if (j == RDV + 8) issue_chunk<true>(p, p.fil_off, 2);
-    }
+    if (j == RDV + 4) issue_chunk<true>(p, p.fil_off, 1);
+    if (j == RDV + 8) issue_chunk<true>(p, p.fil_off, 2);
     __builtin_amdgcn_sched_barrier(0);
   }
   ring_rotate(p);
@@ -709,11 +643,7 @@ __device__ __forceinline__ void sq_chunk(Pipe &p, sq_v8 (&fr)[SQ_NF], const v4uu
 __device__ __forceinline__ void sq_epi_piece(const SqAcc &a, int q, v4uu &oh, v4uu &ol) {
   const float y0 = q == 0 ? a.t0[0] : (q == 1 ? a.t0[2] : (q == 2 ? a.t1[0] : a.t1[2]));
   const float y1 = q == 0 ? a.t0[1] : (q == 1 ? a.t0[3] : (q == 2 ? a.t1[1] : a.t1[3]));
-#ifdef REFNERF_SPLIT_RELU_MAX
-  const float x0 = fmaxf(y0, 0.0f), x1 = fmaxf(y1, 0.0f);
-#else
   const float x0 = (y0 < 0.0f) ? 0.0f : y0, x1 = (y1 < 0.0f) ? 0.0f : y1;
-#endif
   unsigned hi, lo;
   split_pair_f16(x0, x1, hi, lo);
   oh[q] = hi;
@@ -724,7 +654,7 @@ __device__ __forceinline__ void sq_epi_piece(const SqAcc &a, int q, v4uu &oh, v4
 template <bool LAYER0>
 __device__ __forceinline__ void sq_layer(Pipe &p, sq_v8 (&fr)[SQ_NF], SqAcc (&accs)[2], bool skip, const v4uu (&in)[16], v4uu (&out)[16]) {
   /* slice ob accumulates in accs[(ob + 1) & 1]: on entry accs[1] holds the bias of slice 0, on exit that of the first slice
-   * behind this layer (REFNERF_SQ_PREBIAS) */
+   * behind this layer */
 #pragma unroll
   for (int ob = 0; ob < 8; ++ob) {
     SqAcc &acc = accs[(ob + 1) & 1];
@@ -733,11 +663,11 @@ __device__ __forceinline__ void sq_layer(Pipe &p, sq_v8 (&fr)[SQ_NF], SqAcc (&ac
       if (ob == 0 || j >= 8 || (j & 1)) return;
       sq_epi_piece(prev, j >> 1, out[2 * ob - 2], out[2 * ob - 1]);
     };
-    if constexpr (LAYER0) sq_chunk<SQ_X, true, true>(p, fr, in, acc, prev, hook);
+    if constexpr (LAYER0) sq_chunk<SQ_X, true>(p, fr, in, acc, prev, hook);
     else {
-      sq_chunk<SQ_A, true, false>(p, fr, in, acc, prev, hook);
-      sq_chunk<SQ_B, false, true>(p, fr, in, acc, prev);
-      if (skip) sq_chunk<SQ_X, false, true>(p, fr, in, acc, prev);
+      sq_chunk<SQ_A, false>(p, fr, in, acc, prev, hook);
+      sq_chunk<SQ_B, true>(p, fr, in, acc, prev);
+      if (skip) sq_chunk<SQ_X, true>(p, fr, in, acc, prev);
     }
   }
 #pragma unroll
@@ -746,7 +676,6 @@ __device__ __forceinline__ void sq_layer(Pipe &p, sq_v8 (&fr)[SQ_NF], SqAcc (&ac
 }
 /* the bias piece of the chunk in the `cur` slot (the first chunk of a run / of the heads: nothing ran ahead to fetch it) */
 __device__ __forceinline__ void sq_bias_now(const Pipe &p, SqAcc &acc) {
-  if (!REFNERF_SQ_PREBIAS) return;
   const v4f *bp = reinterpret_cast<const v4f *>(p.wbuf + p.cur_off + (p.lane >> 4) * 16);
   acc.t0 = bp[0];
   acc.t1 = bp[4];
@@ -806,7 +735,7 @@ __device__ __forceinline__ void level_fwd_split(const LevelArgs &A) {
    * reads k-group 4 s + b of k-step s: hi plane, the lo plane (BT / 2) * 16 bytes behind */
   p.xps = Xb + ((lane >> 4) * BT + wave * 16 + (lane & 15)) * 16;
   p.seq = 0;
-  p.cur_off = 0; p.nxt_off = BF_CHUNK_BYTES; p.nx2_off = 2 * BF_CHUNK_BYTES; p.fil_off = (REFNERF_RING_SLOTS - 1) * BF_CHUNK_BYTES;
+  p.cur_off = 0; p.nxt_off = BF_CHUNK_BYTES; p.fil_off = 2 * BF_CHUNK_BYTES;
   p.dma_left = n_pass * SPPACKED.chunks_per_pass;
   p.lane = lane; p.wave = wave; p.h = h;
   p.t_vm = 0; p.t_bar = 0;
@@ -816,9 +745,6 @@ __device__ __forceinline__ void level_fwd_split(const LevelArgs &A) {
 #endif
   issue_chunk<true>(p, p.cur_off);                           /* overlaps with the resampler */
   issue_chunk<true>(p, p.nxt_off);
-#if REFNERF_RING_SLOTS == 4
-  issue_chunk<true>(p, p.nx2_off);
-#endif
 
   resample_phase<BF_NW, true>(A, reinterpret_cast<float *>(Xb), TD, NRM, ray0, wave, lane);   /* P0: bit-exact CDF */
   /* (the EXACT resampler leaves the ray geometry to its caller: park it here as the plain kernel's does) */
@@ -841,9 +767,7 @@ __device__ __forceinline__ void level_fwd_split(const LevelArgs &A) {
   __syncthreads();                                           /* chunks 0 and 1 have landed */
   RN_STAMPW(A, 2);
 
-#ifndef REFNERF_BF_NOPRIO
   if (wave >= BF_NW / 2) __builtin_amdgcn_s_setprio(1);
-#endif
   v4uu R0[16], R1[16];
   /* one fragment ring for both sections: four pieces for the 16x16x32 spatial chunks; the plain directional chunks use its
    * first AF entries (the ring always holds the leading pieces of the chunk about to run) */
@@ -913,7 +837,7 @@ __device__ __forceinline__ void level_fwd_split(const LevelArgs &A) {
       for (int ob = 0; ob < 5; ++ob) {
         SqAcc &acc = ha[(ob + 1) & 1];
         if (ob < 4) {
-          sq_chunk<SQ_BN, true, true>(p, ar, R1, acc, ha[ob & 1]);
+          sq_chunk<SQ_BN, true>(p, ar, R1, acc, ha[ob & 1]);
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
             const unsigned pk = e == 0 ? pk_f16(acc.t0[0], acc.t0[1]) : (e == 1 ? pk_f16(acc.t0[2], acc.t0[3])
@@ -926,7 +850,7 @@ __device__ __forceinline__ void level_fwd_split(const LevelArgs &A) {
             }
           }
         } else {
-          sq_chunk<SQ_SC, true, false>(p, ar, R1, acc, ha[ob & 1]);
+          sq_chunk<SQ_SC, false>(p, ar, R1, acc, ha[ob & 1]);
           const int bq = lane_v >> 4;
           int csl = wave * 32 + 16 * run + (lane_v & 15) + 4 * bq * BT;   /* one laundered base: rows are immediate offsets from it */
           asm volatile("" : "+v"(csl));

@@ -60,14 +60,7 @@ struct BwdArgs {
 
 /* A-fragment prefetch depth of the chain GEMMs: the stores riding in the same in-order vmcnt queue make the
  * effective latency of an A load longer than in the forward */
-#ifndef REFNERF_PF_BWD
-#define REFNERF_PF_BWD 3
-#endif
-constexpr int PF_BWD = REFNERF_PF_BWD;
-/* DELTA as bf16 rows in the bf16-chain backward (the chain deltas are bf16-exact; the head / rgb rows get rounded) */
-#ifndef REFNERF_DELTA16
-#define REFNERF_DELTA16 1
-#endif
+constexpr int PF_BWD = 3;
 constexpr int NGS = 7;      /* per-sample upstream gradients (SEEDS rows): density, rgb[3], n_pred[3] */
 
 /* Per-ray part of the backward (one wave per ray): rendering gradient through
@@ -213,7 +206,7 @@ __device__ __forceinline__ void shift_masks(unsigned (&M)[8][4]) {
 template <bool BF, bool SP = false>
 __device__ __forceinline__ void level_bwd_body(const BwdArgs &A) {
   static_assert(!(BF && SP), "one chain arithmetic");
-  constexpr bool D16 = BF && (REFNERF_DELTA16 != 0);
+  constexpr bool D16 = BF;   /* DELTA as bf16 rows in the bf16-chain backward (the chain deltas are bf16-exact; the head / rgb rows get rounded) */
   constexpr int DUNITS = del_units(D16);
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const refnerf_level_cfg &cfg = A.cfg;

@@ -386,16 +386,9 @@ __device__ __forceinline__ void colour_store(const LevelArgs &A, const SampleHea
 
 /* the per-sample history (84 B/sample, 48 MB per launch at C2) is written once and read by a later kernel:
  * non-temporal, so that it does not push the weight image out of the L2s it is streamed from */
-#ifndef REFNERF_HIST_NT
-#define REFNERF_HIST_NT 1
-#endif
-__device__ __forceinline__ void hist_store(float *p, float v) {
-#if REFNERF_HIST_NT
-  __builtin_nontemporal_store(v, p);
-#else
-  *p = v;
-#endif
-}
+__device__ __forceinline__ void hist_store(float *p, float v) { __builtin_nontemporal_store(v, p); }
+/* the same policy as the `aux` operand of a raw buffer store (cache policy bits: sc0 = 1, nt = 2, sc1 = 16) */
+constexpr int AUX_NT = 2;
 
 /* Per-sample history (models.py:731-750) of one wave's 32-sample block, written
  * from LDS PS with fully coalesced stores: for the [R,N,3] tensors lane L writes

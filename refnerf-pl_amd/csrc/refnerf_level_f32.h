@@ -66,15 +66,9 @@ __device__ __forceinline__ void load_acc(__amdgpu_buffer_rsrc_t rs, int off, int
  * through a register ring; sched_barrier pins "MFMAs of step s, then the loads
  * of step s+PF" so that hipcc cannot sink the loads back to their uses (it
  * otherwise emits load; s_waitcnt vmcnt(0); mfma).  lds_steps % PF == 0. */
-#ifndef REFNERF_PF
-#define REFNERF_PF 3
-#endif
-constexpr int PF = REFNERF_PF;
-/* cache policy of the activation / delta streams (written once, read by a later kernel): 2 = nt (streaming,
+constexpr int PF = 3;
+/* the activation / delta streams (written once, read by a later kernel) are stored non-temporal (AUX_NT: streaming,
  * evict-first), so that 9 GB of them per launch do not push the 5 MB weight image out of the 4 MB L2s */
-#ifndef REFNERF_STREAM_AUX
-#define REFNERF_STREAM_AUX 2
-#endif
 struct NoStepHook {
   __device__ __forceinline__ void operator()(int, float) {}
   __device__ __forceinline__ void operator()(int) {}
@@ -121,8 +115,8 @@ struct RowStoreHookT {
       rs = __builtin_amdgcn_make_buffer_rsrc(base + (unsigned long long)(step >> 4) * blk_bytes, 0, 0x80000000, 0x00020000);
       soff = 0;
     }
-    if constexpr (H16) __builtin_amdgcn_raw_buffer_store_b16((unsigned short)(__builtin_bit_cast(unsigned, b) >> 16), rs, voff, soff, REFNERF_STREAM_AUX);
-    else __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, b), rs, voff, soff, REFNERF_STREAM_AUX);
+    if constexpr (H16) __builtin_amdgcn_raw_buffer_store_b16((unsigned short)(__builtin_bit_cast(unsigned, b) >> 16), rs, voff, soff, AUX_NT);
+    else __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, b), rs, voff, soff, AUX_NT);
     soff += ((step & 3) == 3) ? p5 : p1;
   }
 };
@@ -151,7 +145,7 @@ struct PairStoreHook {
       rs = __builtin_amdgcn_make_buffer_rsrc(base + (unsigned long long)(j >> 3) * blk_bytes, 0, 0x80000000, 0x00020000);
       soff = 0;
     }
-    __builtin_amdgcn_raw_buffer_store_b32(dword, rs, voff, soff, REFNERF_STREAM_AUX);
+    __builtin_amdgcn_raw_buffer_store_b32(dword, rs, voff, soff, AUX_NT);
     soff += (j & 1) ? p3 : p1;
   }
 };
@@ -219,10 +213,7 @@ __device__ __forceinline__ void gemm_op(__amdgpu_buffer_rsrc_t rs, int a_off, in
  * that keep the 4 waves in the same L1 window change nothing.
  * The head / rgb recompute and everything per sample stay fp32.
  * ------------------------------------------------------------------------------------------------ */
-#ifndef REFNERF_PF16
-#define REFNERF_PF16 4
-#endif
-constexpr int PF16 = REFNERF_PF16;
+constexpr int PF16 = 4;
 template <int NOB>
 __device__ __forceinline__ void load_a16(__amdgpu_buffer_rsrc_t rs, int voff, int soff, v8bf (&a)[NOB]) {
   /* image layout [k-step][ob][lane][8 bf16]: one instruction = 64 lanes x 16 B = 1 KB contiguous (8 cache lines); the
@@ -423,9 +414,7 @@ __device__ __forceinline__ void smb_load_rows(const float *act, long long pitch,
  * traffic of the per-wave stream (which ran at ~1250 cycles per k-step for 256 cycles of MFMA).  One s_barrier per
  * k-step, no memory fence: the history stores of the hook stay in flight across it (only this wave's ds_writes are
  * waited for).  Must be called by all four waves of the workgroup, the same number of times. */
-#ifndef REFNERF_RING_FETCH
-#define REFNERF_RING_FETCH 4   /* an L2 round trip under load outlasts two k-steps */
-#endif
+constexpr int RING_FETCH = 4;  /* k-steps between a quarter's fetch and its LDS write: an L2 round trip under load outlasts two */
 constexpr int RING_SLOTS = 3;
 constexpr int RING_BYTES = RING_SLOTS * BT_STEP_FLOATS * 4;
 /* BIAS: the accumulators start from the op's bias rows (forward); else from zero (backward: W^T delta) */
@@ -457,7 +446,7 @@ __device__ __forceinline__ void gemm_chain_bf16_shared(__amdgpu_buffer_rsrc_t rs
   };
   /* step s: [fragments of s+1 <- slot (s+1)%3] [MFMAs of s] [stage s+2 -> slot (s+2)%3, fetch s+4] [rendezvous].
    * Slot (s+2)%3 was last read as step s-1, before the rendezvous of step s-1 that every wave has passed. */
-  constexpr int GD = REFNERF_RING_FETCH;                        /* k-steps between a quarter's fetch and its LDS write */
+  constexpr int GD = RING_FETCH;
   v4u g[GD][2];
   v8bf a[2][8];
 #pragma unroll
@@ -636,13 +625,7 @@ __device__ __forceinline__ void mask_split(const v16f (&out)[8], const unsigned 
 
 /* rows [row0 + 32*blk + row(r,h)] of a [rows][pitch] matrix, column gs: 128 B
  * contiguous per (row, half-wave).  Uniform 64-bit row base + 32-bit lane offset. */
-__device__ __forceinline__ void stream_store(float *p, float v) {
-#if REFNERF_STREAM_AUX
-  __builtin_nontemporal_store(v, p);
-#else
-  *p = v;
-#endif
-}
+__device__ __forceinline__ void stream_store(float *p, float v) { __builtin_nontemporal_store(v, p); }
 /* Element (row, col) of a [rows][pitch] matrix: fp32 rows, or (H16) bf16 rows stored in PAIRS -- rows 2j and 2j+1 share
  * the dwords of pair-row j (low / high half), so that a lane's two adjacent features (exactly a packed B-fragment dword)
  * leave in one 4-byte store and a half-wave writes a full 128-B line segment. */
@@ -656,11 +639,7 @@ __device__ __forceinline__ void stream_store_e(float *base, long long idx, float
   if constexpr (H16) {
     unsigned short *q = reinterpret_cast<unsigned short *>(base) + idx;
     const unsigned short w = __builtin_bit_cast(unsigned short, (__bf16)v);
-#if REFNERF_STREAM_AUX
     __builtin_nontemporal_store(w, q);
-#else
-    *q = w;
-#endif
   } else stream_store(base + idx, v);
 }
 template <bool H16>

@@ -136,9 +136,7 @@ __device__ __forceinline__ void level_bwd_sq_body(const SqBwdArgs &A) {
   tq_issue<true>(p, p.nxt_off);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-#ifndef REFNERF_BF_NOPRIO
   if (wave >= BF_NW / 2) __builtin_amdgcn_s_setprio(1);
-#endif
   v4uu R0[16], R1[16];
   v8mm ad[AF];
 #pragma unroll

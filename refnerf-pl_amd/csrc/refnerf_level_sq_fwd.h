@@ -23,10 +23,6 @@
 
 namespace rn {
 
-#ifndef REFNERF_SQ_STREAM_AUX
-#define REFNERF_SQ_STREAM_AUX 2    /* nt: written once, read by a later kernel */
-#endif
-
 /* ---- the pass window of a blocked matrix ([64-sample block][unit][64]): descriptor on the block of the pass's first sample,
  * lane offset = the lane's sample inside it (0xfffffff0: the lane must not store / reads zero) ---- */
 struct BlkWin {
@@ -54,7 +50,7 @@ __device__ __forceinline__ unsigned blk_voff_add(unsigned voff, int lane_units) 
  * works block by block, then finds no add to fold into the immediate field) */
 __device__ __forceinline__ void win_store(const BlkWin &w, unsigned voff, int sunit, int iunit, unsigned dword) {
   asm volatile("" : "+v"(voff));
-  __builtin_amdgcn_raw_buffer_store_b32(dword, w.rs, voff + (unsigned)iunit * 256u, sunit * 256, REFNERF_SQ_STREAM_AUX);
+  __builtin_amdgcn_raw_buffer_store_b32(dword, w.rs, voff + (unsigned)iunit * 256u, sunit * 256, AUX_NT);   /* written once, read by a later kernel */
 }
 __device__ __forceinline__ unsigned win_load(const BlkWin &w, unsigned voff, int sunit, int iunit) {
   asm volatile("" : "+v"(voff));
@@ -97,9 +93,9 @@ __device__ __forceinline__ void tq_issue(Pipe &p, int slot_off, int piece = -1) 
     asm volatile("" : "+s"(wv));
     if (wv < 6) {
       lptr_t dst = (lptr_t)(p.wbuf + slot_off + wv * 3072);
-      if (piece < 0 || piece == 0) __builtin_amdgcn_global_load_lds((gptr_t)p.src, dst, 16, 0, REFNERF_DMA_AUX);
-      if (piece < 0 || piece == 1) __builtin_amdgcn_global_load_lds((gptr_t)p.src, dst, 16, 1024, REFNERF_DMA_AUX);
-      if ((piece < 0 || piece == 2) && wv < 5) __builtin_amdgcn_global_load_lds((gptr_t)p.src, dst, 16, 2048, REFNERF_DMA_AUX);
+      if (piece < 0 || piece == 0) __builtin_amdgcn_global_load_lds((gptr_t)p.src, dst, 16, 0, 0);
+      if (piece < 0 || piece == 1) __builtin_amdgcn_global_load_lds((gptr_t)p.src, dst, 16, 1024, 0);
+      if ((piece < 0 || piece == 2) && wv < 5) __builtin_amdgcn_global_load_lds((gptr_t)p.src, dst, 16, 2048, 0);
     }
     if (piece >= 0 && piece < 2) return;
     p.src += BF_CHUNK_BYTES;
@@ -113,12 +109,6 @@ __device__ __forceinline__ void tq_issue(Pipe &p, int slot_off, int piece = -1) 
     p.dma_left -= 1;
   }
 }
-__device__ __forceinline__ void tq_rotate(Pipe &p) {
-  const int t = p.cur_off;
-  p.cur_off = p.nxt_off;
-  p.nxt_off = p.fil_off;
-  p.fil_off = t;
-}
 /* (round 6) the forward's extra workgroup barrier between the second run's VJP and the directional phase (see P4): an idle wave
  * joins it at the same place in the barrier sequence, behind the 2 TR_RUN rendezvous of the two runs */
 __device__ __forceinline__ void tq_phase_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
@@ -129,7 +119,7 @@ __device__ __forceinline__ void tq_idle_pass(Pipe &p) {
     if (!BWD && c == 2 * TR_RUN) tq_phase_barrier();
     tq_rendezvous<0>(p);
     tq_issue<BWD>(p, p.fil_off);
-    tq_rotate(p);
+    ring_rotate(p);
   }
 }
 
@@ -176,7 +166,7 @@ __device__ __forceinline__ void tq_chunk(Pipe &p, sq_v8 (&fr)[SQ_NF], const v4uu
     if (j == RDV + 8) tq_issue<false>(p, p.fil_off, 2);
     __builtin_amdgcn_sched_barrier(0);
   }
-  tq_rotate(p);
+  ring_rotate(p);
 }
 /* (a chunk of a section without biases: the transposed ops) */
 __device__ __forceinline__ void tq_zero(SqAcc &a) { a.t0 = (v4f){0.0f, 0.0f, 0.0f, 0.0f}; a.t1 = (v4f){0.0f, 0.0f, 0.0f, 0.0f}; }
@@ -219,7 +209,7 @@ __device__ __forceinline__ void tq_bf_chunk(Pipe &p, MmF16::v8 (&a)[AF], const v
     if (k == RDV + 4) tq_issue<BWD>(p, p.fil_off, 2);
     __builtin_amdgcn_sched_barrier(0);
   }
-  tq_rotate(p);
+  ring_rotate(p);
 }
 
 /* x where bit `bit` of `mk` is set, else +0: v_bfe_i32 (0 / all ones) + v_and (keep_if_bit of refnerf_level_f32.h) */
@@ -526,9 +516,7 @@ __device__ __forceinline__ void level_fwd_train_sq_body(const LevelArgs &A) {
   __syncthreads();                                           /* chunks 0 and 1 have landed */
   RN_STAMPW(A, 2);
 
-#ifndef REFNERF_BF_NOPRIO
   if (wave >= BF_NW / 2) __builtin_amdgcn_s_setprio(1);
-#endif
   v4uu R0[16], R1[16];
   sq_v8 ar[SQ_NF];
 #pragma unroll

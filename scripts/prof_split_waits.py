@@ -1,5 +1,6 @@
 """REFNERF_PROF=1 stamps + per-wave DMA-wait / barrier-wait cycles of the split-f16 eval kernel from a -DREFNERF_PROF_WAITS build:
-  python scripts/prof_split_waits.py ab/pw.so"""
+  python scripts/prof_split_waits.py ab/pw.so
+(every rendezvous is timed, those of a wave's idle passes -- a partly filled last pass -- included)"""
 import os, sys
 os.environ["REFNERF_PROF"] = "1"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
