@@ -431,6 +431,46 @@ int refnerf_losses_backward(int32_t R, int32_t N, const float *d_r_rgb, const fl
                             float g_data, float g_orientation, float g_normal, const float *d_upstream,
                             float *d_g_r_rgb, float *d_g_weights, float *d_g_normals_pred, void *stream);
 
+/* The optimiser step of the reference's loop, fused (nerf_system.py:205-217 configure_gradient_clipping +
+ * on_after_backward, torch.optim.Adam.step): clip_grad_value_(grad_max_val), clip_grad_norm_(grad_max_norm) over ALL
+ * tensors of the step, Adam (no AMSGrad, no weight decay), and the per-segment statistics grad_norm = |g|_2 and
+ * grad_max = max|g| of the raw gradient and weight_l2 = |w|_2^2.  fp32 tensors of n < 2^31 elements.
+ *
+ * A tensor is cut into segments by a HOST table seg_off[n_seg + 1] (elements; seg_off[0] = 0 < ... < seg_off[n_seg] = n:
+ * the segments tile [0, n), need no alignment and may be one element long) -- the layers of a flat parameter blob, or one
+ * segment for a plain tensor.  Per tensor the caller owns
+ *   d_workspace  refnerf_optim_workspace_bytes(n, n_seg) bytes, 16-byte aligned; refnerf_optim_plan fills it ONCE with the
+ *                work items (segment, start, length <= 4096) the statistics kernel runs over (a setup call: it
+ *                synchronises the stream) and returns their number;
+ *   d_seg_stats  float [n_seg][3] = { grad_norm, grad_max, weight_l2 }, written by refnerf_optim_finalize;
+ * and per optimiser one d_state of refnerf_optim_state_bytes(max_tensors) bytes, 16-byte aligned: float total_norm,
+ * float clip_coef, double total_norm^2, then the library's table of the step's tensors.
+ * One step = refnerf_optim_stats per tensor (slot = 0 .. k-1: which tensor of THIS step; tensors without a gradient are
+ * simply left out) -> refnerf_optim_finalize(k) -> refnerf_optim_adam_step per tensor: 2k + 1 launches on one stream, no
+ * host synchronisation, no allocation, no float atomics -- every sum has one fixed order, so a step is bit-reproducible.
+ * total_norm is the norm of the value-clipped gradients (what clip_grad_norm_ returns); clip_coef =
+ * min(1, grad_max_norm / (total_norm + 1e-6)), or 1 when grad_max_norm <= 0; a non-finite norm reaches the parameters as
+ * it does in torch.  REFNERF_EINVAL: a null pointer, n <= 0, a table that does not tile [0, n), a workspace or state
+ * too small or misaligned, a slot outside the state. */
+typedef struct refnerf_adam_cfg {
+  double lr, beta1, beta2, eps;
+  double bias_correction1;        /* 1 - beta1^t, t = 1 for the first step */
+  double sqrt_bias_correction2;   /* sqrt(1 - beta2^t) */
+  double grad_max_val;            /* <= 0: no value clipping */
+  int32_t write_grad;             /* also store the clipped gradient back into d_grad */
+  int32_t no_step;                /* clip only (needs write_grad): d_param / d_exp_avg / d_exp_avg_sq may be NULL */
+} refnerf_adam_cfg;
+size_t refnerf_optim_workspace_bytes(int64_t n_elements, int32_t n_segments);   /* 0 for bad arguments */
+size_t refnerf_optim_state_bytes(int32_t max_tensors);
+int refnerf_optim_plan(int64_t n, const int32_t *seg_off, int32_t n_seg, void *d_workspace, size_t workspace_bytes,
+                       int32_t *n_items, void *stream);
+int refnerf_optim_stats(const float *d_grad, const float *d_param, int64_t n, int32_t n_seg, int32_t n_items,
+                        double grad_max_val, void *d_workspace, size_t workspace_bytes, float *d_seg_stats,
+                        void *d_state, size_t state_bytes, int32_t slot, void *stream);
+int refnerf_optim_finalize(void *d_state, size_t state_bytes, int32_t n_tensors, double grad_max_norm, void *stream);
+int refnerf_optim_adam_step(float *d_param, float *d_grad, float *d_exp_avg, float *d_exp_avg_sq, int64_t n,
+                            const refnerf_adam_cfg *cfg, const void *d_state, void *stream);
+
 /* Total duration (ms) and count of the `refnerf_level_forward` kernels launched
  * since refnerf_set_timing(1), from HIP event pairs on the launch stream.
  * Used by bench.py for the roofline line. */

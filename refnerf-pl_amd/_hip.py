@@ -71,6 +71,12 @@ class LensDistortion(C.Structure):
     _fields_ = [(n, C.c_double) for n in ("k1", "k2", "k3", "k4", "p1", "p2", "eps")] + [("max_iterations", C.c_int32)]
 
 
+class AdamCfg(C.Structure):
+    """refnerf_adam_cfg: one Adam step's scalars, computed by the host in double."""
+    _fields_ = [(n, C.c_double) for n in ("lr", "beta1", "beta2", "eps", "bias_correction1", "sqrt_bias_correction2",
+                                          "grad_max_val")] + [("write_grad", C.c_int32), ("no_step", C.c_int32)]
+
+
 class HipLibraryError(RuntimeError):
     pass
 
@@ -131,6 +137,15 @@ def lib():
         L.refnerf_render_rays.argtypes = [C.POINTER(LevelCfg), C.c_int32] + [_FP] * 11 + [C.POINTER(LevelOut), _FP]
         L.refnerf_losses_forward.argtypes = [C.c_int32, C.c_int32] + [_FP] * 9 + [_FP]
         L.refnerf_losses_backward.argtypes = [C.c_int32, C.c_int32] + [_FP] * 5 + [C.c_int32] + [_FP] * 3 + [C.c_float] * 3 + [_FP] * 4 + [_FP]
+        L.refnerf_optim_workspace_bytes.restype = C.c_size_t
+        L.refnerf_optim_workspace_bytes.argtypes = [C.c_int64, C.c_int32]
+        L.refnerf_optim_state_bytes.restype = C.c_size_t
+        L.refnerf_optim_state_bytes.argtypes = [C.c_int32]
+        L.refnerf_optim_plan.argtypes = [C.c_int64, C.POINTER(C.c_int32), C.c_int32, _FP, C.c_size_t, C.POINTER(C.c_int32), _FP]
+        L.refnerf_optim_stats.argtypes = [_FP, _FP, C.c_int64, C.c_int32, C.c_int32, C.c_double, _FP, C.c_size_t, _FP,
+                                          _FP, C.c_size_t, C.c_int32, _FP]
+        L.refnerf_optim_finalize.argtypes = [_FP, C.c_size_t, C.c_int32, C.c_double, _FP]
+        L.refnerf_optim_adam_step.argtypes = [_FP, _FP, _FP, _FP, C.c_int64, C.POINTER(AdamCfg), _FP, _FP]
         L.refnerf_get_timing.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_int64)]
         L.refnerf_get_timing_family.argtypes = [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
         if L.refnerf_abi_version() != ABI_VERSION:
@@ -434,6 +449,67 @@ def losses_backward(r_rgb, gt_rgb, lossmult, weights, orientation_normals, orien
                                         float(g_data), float(g_orientation), float(g_normal), ptr(upstream),
                                         ptr(g_rgb), ptr(g_w), ptr(g_np), stream_ptr()))
     return g_rgb, g_w, g_np
+
+
+def _ptr32(t):
+    """data pointer of an fp32 device tensor; contiguity is the caller's check (views of a blob are welcome)"""
+    if t is None:
+        return None
+    if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+        raise ValueError("the optimiser kernels take contiguous float32 device tensors")
+    return C.c_void_p(t.data_ptr())
+
+
+def optim_state_bytes(max_tensors: int) -> int:
+    return int(lib().refnerf_optim_state_bytes(int(max_tensors)))
+
+
+def optim_state(max_tensors: int, device) -> torch.Tensor:
+    """The optimiser's device state (refnerf_optim_state_bytes): [0:4] total_norm, [4:8] clip_coef as float32."""
+    nbytes = int(lib().refnerf_optim_state_bytes(int(max_tensors)))
+    if nbytes == 0:
+        raise ValueError("optim_state: max_tensors must be positive")
+    return torch.zeros(nbytes, dtype=torch.uint8, device=device)
+
+
+def optim_plan(n: int, seg_off, device):
+    """refnerf_optim_plan for a tensor of n elements cut at `seg_off` (n_seg + 1 element offsets, 0 .. n): allocates and fills
+    the tensor's workspace (a setup call; synchronises).  Returns (workspace, seg_stats [n_seg, 3], n_items)."""
+    require_device()
+    seg = [int(x) for x in seg_off]
+    n_seg = len(seg) - 1
+    nbytes = int(lib().refnerf_optim_workspace_bytes(int(n), n_seg)) if n_seg >= 1 else 0
+    if nbytes == 0 or any(not -2 ** 31 <= x < 2 ** 31 for x in seg):
+        raise ValueError(f"optim_plan: n = {n} with {n_seg} segments is not a valid layout (n in [1, 2^31), 1 <= n_seg <= n)")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    stats = torch.zeros((n_seg, 3), dtype=torch.float32, device=device)
+    n_items = C.c_int32(0)
+    with torch.cuda.device(ws.device):
+        check(lib().refnerf_optim_plan(int(n), (C.c_int32 * (n_seg + 1))(*seg), n_seg, ptr(ws), nbytes, C.byref(n_items), stream_ptr()))
+    return ws, stats, int(n_items.value)
+
+
+def optim_stats(grad, param, n_seg: int, n_items: int, grad_max_val: float, workspace, seg_stats, state, slot: int):
+    """refnerf_optim_stats: the four partial sums per work item of one tensor, and its entry `slot` in the state's table."""
+    if grad.numel() != param.numel():
+        raise ValueError("optim_stats: gradient and parameter differ in size")
+    check(lib().refnerf_optim_stats(_ptr32(grad), _ptr32(param), param.numel(), n_seg, n_items, float(grad_max_val), ptr(workspace),
+                                    workspace.numel(), _ptr32(seg_stats), ptr(state), state.numel(), int(slot), stream_ptr()))
+
+
+def optim_finalize(state, n_tensors: int, grad_max_norm: float):
+    """refnerf_optim_finalize: per-segment statistics of the step's tensors, total_norm and clip_coef into the state."""
+    check(lib().refnerf_optim_finalize(ptr(state), state.numel(), int(n_tensors), float(grad_max_norm), stream_ptr()))
+
+
+def optim_adam_step(param, grad, exp_avg, exp_avg_sq, cfg: AdamCfg, state):
+    """refnerf_optim_adam_step: g = clip_coef * clamp(g), then torch's Adam update in place (cfg.no_step: the clip alone)."""
+    n = grad.numel()
+    for t in (param, exp_avg, exp_avg_sq):
+        if t is not None and t.numel() != n:
+            raise ValueError("optim_adam_step: tensors differ in size")
+    check(lib().refnerf_optim_adam_step(_ptr32(param), _ptr32(grad), _ptr32(exp_avg), _ptr32(exp_avg_sq), n, C.byref(cfg), ptr(state),
+                                        stream_ptr()))
 
 
 def sample_intervals(t, logits, n, smin=0.0, smax=1.0):

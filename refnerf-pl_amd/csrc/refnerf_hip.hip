@@ -30,6 +30,7 @@
 #include "refnerf_wgrad.h"
 #include "refnerf_wgrad_bf16x3.h"
 #include "refnerf_rays.h"
+#include "refnerf_optim.h"
 #include "refnerf_pack_common.h"
 #include "refnerf_sq_host.h"
 #include "refnerf_sq_layout.h"
@@ -1227,6 +1228,119 @@ int refnerf_losses_backward(int32_t R, int32_t N, const float *d_r_rgb, const fl
   a.g_rgb = d_g_r_rgb; a.g_weights = d_g_weights; a.g_npred = d_g_normals_pred;
   const size_t n = (size_t)R * N;
   hipLaunchKernelGGL(rn::refnerf_losses_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+  HIP_TRY(hipGetLastError());
+  return REFNERF_OK;
+}
+
+/* ---- the optimiser step (refnerf_optim.h) ---- */
+namespace {
+struct OptimLayout { size_t max_items, items_off, partials_off, segitem_off, total; };
+bool optim_layout(int64_t n, int32_t n_seg, OptimLayout *L) {
+  if (n <= 0 || n > INT32_MAX || n_seg <= 0 || (int64_t)n_seg > n) return false;
+  L->max_items = (size_t)((n + rn::OPTIM_CHUNK - 1) / rn::OPTIM_CHUNK) + (size_t)n_seg;
+  L->items_off = 0;
+  L->partials_off = L->max_items * sizeof(rn::OptimItem);
+  L->segitem_off = L->partials_off + L->max_items * 4 * sizeof(float);
+  L->total = L->segitem_off + (((size_t)n_seg + 1) * sizeof(int32_t) + 15) / 16 * 16;
+  return true;
+}
+}  // namespace
+
+size_t refnerf_optim_workspace_bytes(int64_t n_elements, int32_t n_segments) {
+  OptimLayout L;
+  return optim_layout(n_elements, n_segments, &L) ? L.total : 0;
+}
+
+size_t refnerf_optim_state_bytes(int32_t max_tensors) {
+  return max_tensors <= 0 ? 0 : rn::OPTIM_STATE_HEADER + (size_t)max_tensors * sizeof(rn::OptimDesc);
+}
+
+int refnerf_optim_plan(int64_t n, const int32_t *seg_off, int32_t n_seg, void *d_workspace, size_t workspace_bytes,
+                       int32_t *n_items, void *stream) {
+  OptimLayout L;
+  if (!seg_off || !d_workspace || !n_items) return fail(REFNERF_EINVAL, "refnerf_optim_plan: null pointer%s");
+  if (!optim_layout(n, n_seg, &L)) return fail(REFNERF_EINVAL, "refnerf_optim_plan: n must be in [1, 2^31) and n_seg in [1, n]%s");
+  if (workspace_bytes < L.total || ((uintptr_t)d_workspace & 15u)) return fail(REFNERF_EINVAL, "refnerf_optim_plan: workspace too small or not 16-byte aligned%s");
+  if (seg_off[0] != 0 || (int64_t)seg_off[n_seg] != n) return fail(REFNERF_EINVAL, "refnerf_optim_plan: the segment table does not tile [0, n)%s");
+  for (int32_t s = 0; s < n_seg; ++s)
+    if (seg_off[s + 1] <= seg_off[s]) return fail(REFNERF_EINVAL, "refnerf_optim_plan: the segment table does not tile [0, n) (offsets must increase)%s");
+  std::vector<unsigned char> img(L.total, 0);
+  rn::OptimItem *items = reinterpret_cast<rn::OptimItem *>(img.data() + L.items_off);
+  int32_t *seg_item = reinterpret_cast<int32_t *>(img.data() + L.segitem_off);
+  int32_t k = 0;
+  for (int32_t s = 0; s < n_seg; ++s) {
+    seg_item[s] = k;
+    for (int32_t at = seg_off[s]; at < seg_off[s + 1]; at += rn::OPTIM_CHUNK) {
+      const int32_t len = seg_off[s + 1] - at < rn::OPTIM_CHUNK ? seg_off[s + 1] - at : rn::OPTIM_CHUNK;
+      items[k++] = rn::OptimItem{s, at, len, 0};
+    }
+  }
+  seg_item[n_seg] = k;
+  if ((size_t)k > L.max_items) return fail(REFNERF_EINVAL, "refnerf_optim_plan: internal error (work items)%s");
+  /* a setup call: the host image must outlive the copy */
+  HIP_TRY(hipMemcpyAsync(d_workspace, img.data(), L.total, hipMemcpyHostToDevice, (hipStream_t)stream));
+  HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+  *n_items = k;
+  return REFNERF_OK;
+}
+
+int refnerf_optim_stats(const float *d_grad, const float *d_param, int64_t n, int32_t n_seg, int32_t n_items,
+                        double grad_max_val, void *d_workspace, size_t workspace_bytes, float *d_seg_stats,
+                        void *d_state, size_t state_bytes, int32_t slot, void *stream) {
+  OptimLayout L;
+  if (!d_grad || !d_param || !d_workspace || !d_seg_stats || !d_state) return fail(REFNERF_EINVAL, "refnerf_optim_stats: null pointer%s");
+  if (!optim_layout(n, n_seg, &L)) return fail(REFNERF_EINVAL, "refnerf_optim_stats: n must be in [1, 2^31) and n_seg in [1, n]%s");
+  if (workspace_bytes < L.total || ((uintptr_t)d_workspace & 15u)) return fail(REFNERF_EINVAL, "refnerf_optim_stats: workspace too small or not 16-byte aligned%s");
+  if (n_items < n_seg || (size_t)n_items > L.max_items) return fail(REFNERF_EINVAL, "refnerf_optim_stats: n_items is not what refnerf_optim_plan returned%s");
+  if (((uintptr_t)d_grad & 3u) || ((uintptr_t)d_param & 3u) || ((uintptr_t)d_state & 15u)) return fail(REFNERF_EINVAL, "refnerf_optim_stats: misaligned pointer%s");
+  if (slot < 0 || state_bytes < refnerf_optim_state_bytes(slot + 1)) return fail(REFNERF_EINVAL, "refnerf_optim_stats: slot outside the state%s");
+  unsigned char *ws = static_cast<unsigned char *>(d_workspace);
+  rn::OptimDesc d;
+  d.seg_item_off = reinterpret_cast<const int32_t *>(ws + L.segitem_off);
+  d.partials = reinterpret_cast<const float *>(ws + L.partials_off);
+  d.seg_stats = d_seg_stats;
+  d.n_seg = n_seg;
+  d.n_items = n_items;
+  rn::OptimDesc *slot_ptr = reinterpret_cast<rn::OptimDesc *>(static_cast<unsigned char *>(d_state) + rn::OPTIM_STATE_HEADER) + slot;
+  hipLaunchKernelGGL(rn::optim_stats_kernel, dim3((unsigned)n_items), dim3(rn::OPTIM_THREADS), 0, (hipStream_t)stream, d_grad, d_param,
+                     (int32_t)n, reinterpret_cast<const rn::OptimItem *>(ws + L.items_off), reinterpret_cast<float *>(ws + L.partials_off),
+                     (float)grad_max_val, d, slot_ptr);
+  HIP_TRY(hipGetLastError());
+  return REFNERF_OK;
+}
+
+int refnerf_optim_finalize(void *d_state, size_t state_bytes, int32_t n_tensors, double grad_max_norm, void *stream) {
+  if (!d_state || ((uintptr_t)d_state & 15u)) return fail(REFNERF_EINVAL, "refnerf_optim_finalize: null or misaligned state%s");
+  if (n_tensors <= 0 || state_bytes < refnerf_optim_state_bytes(n_tensors)) return fail(REFNERF_EINVAL, "refnerf_optim_finalize: n_tensors outside the state%s");
+  hipLaunchKernelGGL(rn::optim_finalize_kernel, dim3(1), dim3(rn::OPTIM_THREADS), 0, (hipStream_t)stream,
+                     static_cast<unsigned char *>(d_state), n_tensors, (float)grad_max_norm);
+  HIP_TRY(hipGetLastError());
+  return REFNERF_OK;
+}
+
+int refnerf_optim_adam_step(float *d_param, float *d_grad, float *d_exp_avg, float *d_exp_avg_sq, int64_t n,
+                            const refnerf_adam_cfg *cfg, const void *d_state, void *stream) {
+  if (!cfg || !d_grad || !d_state) return fail(REFNERF_EINVAL, "refnerf_optim_adam_step: null pointer%s");
+  if (!cfg->no_step && (!d_param || !d_exp_avg || !d_exp_avg_sq)) return fail(REFNERF_EINVAL, "refnerf_optim_adam_step: null pointer%s");
+  if (cfg->no_step && !cfg->write_grad) return fail(REFNERF_EINVAL, "refnerf_optim_adam_step: no_step without write_grad does nothing%s");
+  if (n <= 0 || n > INT32_MAX) return fail(REFNERF_EINVAL, "refnerf_optim_adam_step: n must be in [1, 2^31)%s");
+  if (((uintptr_t)d_param | (uintptr_t)d_grad | (uintptr_t)d_exp_avg | (uintptr_t)d_exp_avg_sq | (uintptr_t)d_state) & 3u)
+    return fail(REFNERF_EINVAL, "refnerf_optim_adam_step: misaligned pointer%s");
+  if (!cfg->no_step && !(cfg->bias_correction1 > 0.0 && cfg->sqrt_bias_correction2 > 0.0))
+    return fail(REFNERF_EINVAL, "refnerf_optim_adam_step: bias corrections must be positive (t >= 1)%s");
+  rn::OptimAdamArgs a;
+  a.p = d_param; a.g = d_grad; a.m = d_exp_avg; a.v = d_exp_avg_sq;
+  a.n = (int32_t)n;
+  a.grad_max_val = (float)cfg->grad_max_val;
+  a.w1 = (float)(1.0 - cfg->beta1); a.beta2 = (float)cfg->beta2; a.w2 = (float)(1.0 - cfg->beta2);
+  a.step_size = cfg->no_step ? 0.0f : (float)(cfg->lr / cfg->bias_correction1);
+  a.sqrt_bc2 = (float)cfg->sqrt_bias_correction2; a.eps = (float)cfg->eps;
+  a.write_grad = cfg->write_grad; a.no_step = cfg->no_step;
+  a.clip_coef = static_cast<const float *>(d_state) + 1;
+  const int64_t nvec = (n + 3) / 4;
+  int64_t blocks = (nvec + rn::OPTIM_THREADS - 1) / rn::OPTIM_THREADS;
+  blocks = blocks < 1 ? 1 : (blocks > 4096 ? 4096 : blocks);
+  hipLaunchKernelGGL(rn::optim_adam_kernel, dim3((unsigned)blocks), dim3(rn::OPTIM_THREADS), 0, (hipStream_t)stream, a);
   HIP_TRY(hipGetLastError());
   return REFNERF_OK;
 }

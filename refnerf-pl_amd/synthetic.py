@@ -183,3 +183,39 @@ def llff_rays(n_rays: int, seed: int = 1, width: int = 1008, height: int = 756, 
 
 def target_rgb(n_rays: int, seed: int = 2) -> np.ndarray:
     return hash_uniform(seed, 3, n_rays * 3).reshape(n_rays, 3).astype(np.float32)
+
+
+# --------------------------------------------------------------------------
+# the synthetic optimiser trajectories of tests/golden/optim.npz (make_golden_optim.py and tests/test_optim.py)
+OPTIM_N = 70003
+OPTIM_SEGMENTS = (1, 3, 5, 1021, 4096, 4097, 12288, 16389, OPTIM_N - 37900)   # lengths; they tile [0, OPTIM_N)
+OPTIM_STEPS = 8
+# (grad_max_val, grad_max_norm, gradient scale): both clips, each alone, none, and gradients near adam_eps
+OPTIM_CLIPS = {"norm": (0.0, 1e-3, 1.0), "val_norm": (1e-3, 1e-3, 1.0), "val": (0.1, 0.0, 1.0), "none": (0.0, 0.0, 1.0),
+               "tiny": (0.0, 1e-3, 1e-3)}
+
+
+def optim_params(n: int, seed: int = 11) -> np.ndarray:
+    """Initial parameters of a synthetic optimiser trajectory: U(+-0.1), float32."""
+    return ((hash_uniform(seed, 0, n) * 2.0 - 1.0) * 0.1).astype(np.float32)
+
+
+def optim_gradient(n: int, step: int, scale: float = 1.0, seed: int = 11) -> np.ndarray:
+    """Gradient of step `step` (0-based), float32: U(+-s) with every 17th element x 50, so that value clipping bites;
+    s = 1e-2 * scale on even steps (global norm far above 1e-3: clip_coef < 1) and 1e-7 * scale on odd steps (norm below
+    1e-3: clip_coef = 1)."""
+    g = (hash_uniform(seed, 1 + step, n) * 2.0 - 1.0) * ((1e-2 if step % 2 == 0 else 1e-7) * scale)
+    g[::17] *= 50.0
+    return g.astype(np.float32)
+
+
+def optim_sample_index(n: int) -> np.ndarray:
+    """The elements of a length-n trajectory that optim.npz stores (the whole of it would be 30 MB): everything below 1030
+    (the four short segments of OPTIM_SEGMENTS), four elements either side of every later segment boundary, the last eight,
+    and every 97th."""
+    if n <= 2048:
+        return np.arange(n)
+    idx = [np.arange(1030), np.arange(0, n, 97), np.arange(n - 8, n)]
+    for b in np.cumsum(OPTIM_SEGMENTS)[:-1]:
+        idx.append(np.arange(max(b - 4, 0), min(b + 4, n)))
+    return np.unique(np.concatenate(idx))

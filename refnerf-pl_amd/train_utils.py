@@ -6,11 +6,14 @@ interlevel_loss (:150-162), predicted_normal_loss (:186-204), noisy_consistency_
 (:282-310), accumulated_weights_loss (:313-316), weights_entropy_loss (:318-329) and the loss assembly of
 NeRFSystem.training_step (nerf_system.py:77-188) as `training_losses`.  They are a few elementwise torch
 ops on the level outputs; their gradients w.r.t. the renderings / ray_history entries are the seeds
-refnerf_level_backward consumes (models.py::_LevelFunction).  Optimiser / LR-schedule plumbing is outside
-the hot path.
+refnerf_level_backward consumes (models.py::_LevelFunction).  The optimiser side of the step -- the LR schedule,
+create_optimizer (train_utils.py:448-467) and the two gradient clips of nerf_system.configure_gradient_clipping --
+is at the end of this file; its kernels are optim.ClippedAdam's.
 """
 import collections
+import functools
 
+import numpy as np
 import torch
 
 
@@ -460,3 +463,102 @@ _FINITE_GUARD = _FiniteGuard()
 def flush_finite_check(config=None):
     """raise now if the LAST watched training loss was not finite (call at the end of a run / before a checkpoint)"""
     _FINITE_GUARD.flush(config)
+
+
+# ---- the optimiser side of the step ------------------------------------------------------------------------------------
+def log_lerp(t, v0, v1):
+    """The geometric blend of two positive values, v0 at t <= 0 and v1 at t >= 1: v0^(1-t) v1^t (the reference's
+    math.log_lerp, internal/math.py:37-43, which a ValueError for a non-positive end comes from as well).  numpy double."""
+    ends = np.array([v0, v1], np.float64)
+    if not np.all(ends > 0.0):
+        raise ValueError(f"log_lerp: both ends must be positive to blend geometrically, got v0 = {v0}, v1 = {v1}")
+    u = np.float64(min(max(float(t), 0.0), 1.0))
+    return np.power(ends[0], 1.0 - u) * np.power(ends[1], u)
+
+
+def _warmup_factor(step, lr_delay_steps, lr_delay_mult):
+    """The delay ramp of the schedule: a quarter sine wave from lr_delay_mult at step 0 up to 1 at lr_delay_steps and after
+    (1 throughout when there is no delay)."""
+    if lr_delay_steps <= 0:
+        return np.float64(1.0)
+    phase = min(max(float(step) / float(lr_delay_steps), 0.0), 1.0)
+    mult = np.float64(lr_delay_mult)
+    return mult + (1.0 - mult) * np.sin(np.float64(phase) * (np.pi / 2.0))
+
+
+def learning_rate_decay(step, lr_init, lr_final, max_steps, lr_delay_steps=0, lr_delay_mult=1):
+    """The LambdaLR multiplier at `step`, signature and values of the reference's math.learning_rate_decay
+    (internal/math.py:46-78): the rate falls geometrically from lr_init (step 0) to lr_final (max_steps and after), under
+    the delay ramp of _warmup_factor; returned relative to lr_init.  numpy double throughout."""
+    rate = log_lerp(float(step) / float(max_steps), lr_init, lr_final)
+    return _warmup_factor(step, lr_delay_steps, lr_delay_mult) * rate / np.float64(lr_init)
+
+
+def _distinct_mlps(model):
+    mlps = [("nerf_mlp", model.nerf_mlp)]
+    if model.prop_mlp is not model.nerf_mlp:
+        mlps.insert(0, ("prop_mlp", model.prop_mlp))
+    return mlps
+
+
+def _optimizer_tensors(config, params_or_model):
+    """(tensors, segments, names, mlps): what an optimiser over a Model (or a plain iterable of tensors) steps.  A Model with
+    Config.hip_flat_grads: each distinct MLP's flat_parameter(), cut into its layers' weights and biases; otherwise
+    model.parameters().  The names are the reference's statistics keys (state_dict names with '.' -> '/')."""
+    if not isinstance(params_or_model, torch.nn.Module):
+        return list(params_or_model), {}, {}, []
+    model = params_or_model
+    mlps = _distinct_mlps(model) if hasattr(model, "nerf_mlp") else []
+    if mlps and getattr(config, "hip_flat_grads", False):
+        tensors, segments = [], {}
+        for attr, mlp in mlps:
+            flat = mlp.flat_parameter()
+            names, off = [], []
+            for spec in mlp.specs:
+                names += [f"{attr}/{spec.name}/weight".replace(".", "/"), f"{attr}/{spec.name}/bias".replace(".", "/")]
+                off += [spec.w_off, spec.b_off]
+            tensors.append(flat)
+            segments[id(flat)] = (names, off + [mlp.num_params])
+        return tensors, segments, {}, [m for _, m in mlps]
+    named = list(model.named_parameters())
+    return [p for _, p in named], {}, {id(p): k.replace(".", "/") for k, p in named}, [m for _, m in mlps]
+
+
+def create_optimizer(config, params_or_model, fused_clipping=True):
+    """(optimizer, LambdaLR) as the reference's train_utils.create_optimizer (:448-467) returns them: Adam with Config's
+    lr_init / adam_beta1 / adam_beta2 / adam_eps under math.learning_rate_decay -- here optim.ClippedAdam, which also does
+    the reference's two gradient clips (Config.grad_max_val, grad_max_norm) and its per-parameter statistics inside the
+    step.  fused_clipping=False leaves the clipping to the caller (clip_gradients), which is the reference's split.
+    Handed a Model, it steps the flat blob(s) under Config.hip_flat_grads and model.parameters() otherwise, and a step
+    post-hook calls mark_updated() on each MLP, so the weight-image cache needs no attention from the loop.
+    Set Config.hip_flat_grads for speed: the step is 3 launches (56 us) on the flat blob, but two host calls per tensor on the
+    46 separate parameters of the default mode -- 957 us, slower than torch's foreach sequence (254 us; docs/EXPERIMENTS.md
+    section 12).  The per-tensor mode is there for parity with the reference's layout (its checkpoints' optimizer_states
+    load into it), not for throughput."""
+    from . import optim
+    tensors, segments, names, mlps = _optimizer_tensors(config, params_or_model)
+    optimizer = optim.ClippedAdam(tensors, lr=config.lr_init, betas=(config.adam_beta1, config.adam_beta2), eps=config.adam_eps,
+                                  grad_max_val=config.grad_max_val if fused_clipping else 0.0,
+                                  grad_max_norm=config.grad_max_norm if fused_clipping else 0.0, segments=segments, names=names)
+    if mlps:
+        def _mark_updated(_opt, _args, _kwargs):
+            for mlp in mlps:
+                mlp.mark_updated()
+        optimizer.register_step_post_hook(_mark_updated)
+    lr_scheduler = torch.optim.lr_scheduler.LambdaLR(optimizer, functools.partial(
+        learning_rate_decay, lr_init=config.lr_init, lr_final=config.lr_final, max_steps=config.max_steps,
+        lr_delay_steps=config.lr_delay_steps, lr_delay_mult=config.lr_delay_mult))
+    return optimizer, lr_scheduler
+
+
+def clip_gradients(params_or_model, config):
+    """nerf_system.configure_gradient_clipping (:205-210) alone: clip_grad_value_(Config.grad_max_val) then
+    clip_grad_norm_(Config.grad_max_norm) over all the tensors, written back into their .grad (device tensors: the
+    statistics, finalize and write-back kernels; 2 k + 1 launches).  Returns the ClippedAdam that did it: its stats()
+    carry total_norm and the per-parameter statistics; keep it and call its clip_gradients() to spare the setup."""
+    from . import optim
+    tensors, segments, names, _ = _optimizer_tensors(config, params_or_model)
+    clipper = optim.ClippedAdam(tensors, lr=0.0, grad_max_val=config.grad_max_val, grad_max_norm=config.grad_max_norm,
+                                segments=segments, names=names)
+    clipper.clip_gradients()
+    return clipper
