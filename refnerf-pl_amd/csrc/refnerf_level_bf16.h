@@ -79,14 +79,21 @@ typedef __attribute__((address_space(1))) const void *gptr_t;
 typedef __attribute__((address_space(3))) void *lptr_t;
 
 struct Pipe {
+  /* eval kernels: the DMA source of a piece is a wave-uniform address (scalar registers: the instruction's base operand) +
+   * lane_off (+ the piece's immediate).  Split image: `sp` is the chunk the next DMA fetches, it moves on one chunk per
+   * rendezvous.  Plain image: `sp` is the image, `pos` the chunk's byte offset in it, wrapping on a compare. */
+  const char *sp;
+  unsigned pos;
+  unsigned lane_off; /* wave * 3072 + lane * 16: this lane's place in a chunk (formed once per pass) */
+  /* training kernels (tq_issue): a per-lane pointer and a chunk count */
   const char *src;   /* this lane's DMA source inside the image: advances one chunk per rendezvous */
   const char *src_end;   /* end of one pass worth of chunks (wrap point) for this lane */
   char *wbuf;        /* LDS ring base (3 slots) */
   const char *xp;    /* LDS encodings, pre-offset to this lane's B fragment (sample n, half h) */
   const char *xps;   /* split mode: this lane's B fragment in the IPE planes of a run (hi plane; the lo plane (BT / 2) * 16 bytes behind) */
-  int seq;           /* split mode: chunks issued so far in this pass (the spatial section is streamed twice) */
+  int seq;           /* training kernels: chunks issued so far in this pass (the spatial section is streamed twice) */
   int cur_off, nxt_off, fil_off;   /* ring slots: being consumed / landed next / free */
-  int dma_left;      /* chunks still to be DMA'd by this workgroup */
+  int dma_left;      /* chunks still to be DMA'd: by this WAVE (eval kernels: zero in the waves that issue none) / by the workgroup (training kernels) */
   int lane, wave, h;
   long long t_vm, t_bar;   /* debug (-DREFNERF_PROF_WAITS): cycles spent in the DMA wait / in the barrier */
 };
@@ -120,27 +127,45 @@ __device__ __forceinline__ void ring_rotate(Pipe &p) {
  * behind the rendezvous (an LDS-DMA piece costs its wave 100-185 issue cycles inside a burst, ~60 among MFMAs:
  * MI355X_MICROARCH.md); `piece` = 0, 1, 2, or -1 for all three.  Measured (round 4): f16x2 4.865 -> 4.839 ms per step,
  * bf16 2.105 -> 2.086, results bit-identical.  The DMA keeps the default cache policy (aux 0: `nt` measured +14 %, `sc1` nothing). */
+/* The stream position is scalar: the chunk's address goes into the DMA as its scalar base operand, the lane's part never
+ * changes.  After the last piece the position moves on by `adv` bytes.  The split image is streamed [spatial][spatial]
+ * [directional] per pass, and the stream runs two chunks ahead of the chunk being consumed, so the two places of a pass where
+ * it jumps back are known where the code is written (SP_ADV_REWIND, SP_ADV_WRAP: level_fwd_split); the plain image wraps on a
+ * compare.
+ * ONE scalar test per issue site: `dma_left` counts the chunks THIS WAVE still has pieces to issue for -- the workgroup's
+ * chunk count in waves 0-5, zero in waves 6 and 7 -- so "the stream has not ended" and "this wave issues" are one compare.
+ * (Without any loop-variant test at the issue sites -- a stream that never ends, the wave test alone -- hipcc spills 56-59
+ * registers in every eval kernel: docs/EXPERIMENTS.md section 13.) */
+static_assert(SPPACKED.sp_chunks == 8 + 7 * 16 + 8 + 5 && SPPACKED.total_chunks - SPPACKED.sp_chunks == 8 + 7 * 8 + 8 + 1,
+              "the places where level_fwd_split moves the stream position back are written for this chunk sequence");
+constexpr int SP_ADV_REWIND = (1 - SPPACKED.sp_chunks) * BF_CHUNK_BYTES;      /* end of the first spatial run: back to chunk 0 */
+constexpr int SP_ADV_WRAP = (1 - SPPACKED.total_chunks) * BF_CHUNK_BYTES;     /* end of the pass: back to chunk 0 */
 template <bool SPLIT = false>
-__device__ __forceinline__ void issue_chunk(Pipe &p, int slot_off, int piece = -1) {
-  if (p.dma_left > 0) {
-    if (p.wave < 6) {
-      lptr_t dst = (lptr_t)(p.wbuf + slot_off + p.wave * 3072);
-      if (piece < 0 || piece == 0) __builtin_amdgcn_global_load_lds((gptr_t)p.src, dst, 16, 0, 0);
-      if (piece < 0 || piece == 1) __builtin_amdgcn_global_load_lds((gptr_t)p.src, dst, 16, 1024, 0);
-      if ((piece < 0 || piece == 2) && p.wave < 5) __builtin_amdgcn_global_load_lds((gptr_t)p.src, dst, 16, 2048, 0);
-    }
-    if (piece >= 0 && piece < 2) return;             /* the stream position moves on with the last piece */
-    p.src += BF_CHUNK_BYTES;
-    if constexpr (SPLIT) {
-      /* a pass streams [spatial section][spatial section][directional section] */
-      p.seq += 1;
-      if (p.seq == SPPACKED.sp_chunks) p.src -= (size_t)SPPACKED.sp_chunks * BF_CHUNK_BYTES;
-      else if (p.seq == SPPACKED.chunks_per_pass) { p.src -= (size_t)SPPACKED.total_chunks * BF_CHUNK_BYTES; p.seq = 0; }
-    } else {
-      if (p.src == p.src_end) p.src -= (size_t)BFPACKED.chunks_per_pass * BF_CHUNK_BYTES;
-    }
-    p.dma_left -= 1;
+__device__ __forceinline__ void issue_chunk(Pipe &p, int slot_off, int piece = -1, int adv = BF_CHUNK_BYTES) {
+  if (p.dma_left <= 0) return;
+  lptr_t dst = (lptr_t)(p.wbuf + slot_off + p.wave * 3072);
+  /* laundered HERE: the 32-bit lane offset must meet the scalar base in the block of the DMA, or the compiler widens it once,
+   * carries a 64-bit pair and adds on the vector side */
+  asm volatile("" : "+v"(p.lane_off));
+  gptr_t src = (gptr_t)((SPLIT ? p.sp : p.sp + p.pos) + p.lane_off);
+  if (piece < 0 || piece == 0) __builtin_amdgcn_global_load_lds(src, dst, 16, 0, 0);
+  if (piece < 0 || piece == 1) __builtin_amdgcn_global_load_lds(src, dst, 16, 1024, 0);
+  if ((piece < 0 || piece == 2) && p.wave < 5) __builtin_amdgcn_global_load_lds(src, dst, 16, 2048, 0);
+  if (piece >= 0 && piece < 2) return;               /* the stream position moves on with the last piece */
+  p.dma_left -= 1;
+  if constexpr (SPLIT) p.sp += adv;
+  else {
+    p.pos += BF_CHUNK_BYTES;
+    p.pos = (p.pos == (unsigned)BFPACKED.chunks_per_pass * BF_CHUNK_BYTES) ? 0u : p.pos;
   }
+}
+/* the stream's state at the start of a kernel; `chunks` = what the workgroup streams in all */
+__device__ __forceinline__ void pipe_stream_init(Pipe &p, const void *image, int chunks, int wave, int lane) {
+  p.sp = reinterpret_cast<const char *>(image);
+  p.pos = 0;
+  p.lane_off = (unsigned)(wave * 3072 + lane * 16);
+  p.dma_left = wave < 6 ? chunks : 0;
+  p.src = nullptr; p.src_end = nullptr; p.seq = 0;
 }
 
 template <typename MM>
@@ -194,7 +219,7 @@ struct NoHook { __device__ __forceinline__ void operator()(int) const {} };
 /* `hook(k)`: VALU work of the caller placed behind the MFMA of step k (the split kernel runs the epilogue of the previous
  * slice there, in the issue gaps of this slice's matrix instructions) */
 template <typename MM, int KIND, int REAL_L, bool FIRST, bool SPLIT = false, typename Hook = NoHook>
-__device__ __forceinline__ void bf_chunk(Pipe &p, typename MM::v8 (&a)[AF], const v4uu (&in)[16], const v4uu (&bn)[8], v16f &acc, Hook &&hook = Hook()) {
+__device__ __forceinline__ void bf_chunk(Pipe &p, typename MM::v8 (&a)[AF], const v4uu (&in)[16], const v4uu (&bn)[8], v16f &acc, Hook &&hook = Hook(), int adv = BF_CHUNK_BYTES) {
   typedef typename MM::v8 v8mm;
   constexpr int KS = (KIND == BF_LDS8) ? 8 : 16;
   constexpr int L0 = (KIND == BF_BNLDS) ? 8 : 0;      /* first LDS step (for the LDS kinds) */
@@ -228,7 +253,7 @@ __device__ __forceinline__ void bf_chunk(Pipe &p, typename MM::v8 (&a)[AF], cons
       issue_chunk<SPLIT>(p, p.fil_off, 0);
     }
     if (k == RDV + 2) issue_chunk<SPLIT>(p, p.fil_off, 1);
-    if (k == RDV + 4) issue_chunk<SPLIT>(p, p.fil_off, 2);
+    if (k == RDV + 4) issue_chunk<SPLIT>(p, p.fil_off, 2, adv);
     __builtin_amdgcn_sched_barrier(0);
   }
   ring_rotate(p);
@@ -243,7 +268,8 @@ __device__ __forceinline__ void idle_pass(Pipe &p) {
 #pragma unroll 1
   for (int c = 0; c < (SPLIT ? SPPACKED.chunks_per_pass : BFPACKED.chunks_per_pass); ++c) {
     RN_RENDEZVOUS(p);
-    issue_chunk<SPLIT>(p, p.fil_off);
+    /* chunk c of the pass is the one being "consumed": the DMA fetches chunk c + 2, the position moves on to chunk c + 3 */
+    issue_chunk<SPLIT>(p, p.fil_off, -1, c + 3 == SPPACKED.sp_chunks ? SP_ADV_REWIND : (c + 3 == SPPACKED.chunks_per_pass ? SP_ADV_WRAP : BF_CHUNK_BYTES));
     ring_rotate(p);
   }
 }
@@ -316,12 +342,10 @@ __device__ __forceinline__ void level_fwd_mm(const LevelArgs &A) {
   const int col = wave * 32 + n;                             /* this lane's sample column */
 
   Pipe p;
-  p.src = reinterpret_cast<const char *>(A.packed) + wave * 3072 + lane * 16;
-  p.src_end = p.src + (size_t)BFPACKED.chunks_per_pass * BF_CHUNK_BYTES;
+  pipe_stream_init(p, A.packed, n_pass * BFPACKED.chunks_per_pass, wave, lane);
   p.wbuf = WB;
   p.xp = Xb + (h * BT + col) * 16;
   p.cur_off = 0; p.nxt_off = BF_CHUNK_BYTES; p.fil_off = 2 * BF_CHUNK_BYTES;
-  p.dma_left = n_pass * BFPACKED.chunks_per_pass;
   p.lane = lane; p.wave = wave; p.h = h;
   p.t_vm = 0; p.t_bar = 0;
   RN_STAMPW(A, 0);
@@ -347,6 +371,7 @@ __device__ __forceinline__ void level_fwd_mm(const LevelArgs &A) {
      * arithmetic out of the pass loop (it then spills them to scratch) */
     int lane_v = lane, col_v = col;
     asm volatile("" : "+v"(lane_v), "+v"(col_v));
+    p.lane_off = (unsigned)(wave * 3072 + lane_v * 16);
     /* which (ray, sample) this lane's column is: recomputed at every use (P1, P4, P6) from laundered inputs instead of being
      * carried -- spilled -- across the MLP phases */
     auto locate = [&](int &g, int &rl, int &si, bool &valid) {
@@ -594,7 +619,7 @@ template <int KIND> constexpr int sq_release(int j) {
  * bias piece of the NEXT chunk into `nacc` right behind its rendezvous) -- instead of loading it and waiting a full LDS round
  * trip in front of its first MFMA */
 template <int KIND, bool PRE, typename Hook = NoHook>
-__device__ __forceinline__ void sq_chunk(Pipe &p, sq_v8 (&fr)[SQ_NF], const v4uu (&in)[16], SqAcc &acc, SqAcc &nacc, Hook &&hook = Hook()) {
+__device__ __forceinline__ void sq_chunk(Pipe &p, sq_v8 (&fr)[SQ_NF], const v4uu (&in)[16], SqAcc &acc, SqAcc &nacc, Hook &&hook = Hook(), int adv = BF_CHUNK_BYTES) {
   constexpr int NM = sq_nm<KIND>(), NP = sq_np<KIND>();
   constexpr int RDV = NM / 2 - 1;
   const char *w = p.wbuf + p.cur_off;
@@ -633,7 +658,7 @@ __device__ __forceinline__ void sq_chunk(Pipe &p, sq_v8 (&fr)[SQ_NF], const v4uu
       }
     }
     if (j == RDV + 4) issue_chunk<true>(p, p.fil_off, 1);
-    if (j == RDV + 8) issue_chunk<true>(p, p.fil_off, 2);
+    if (j == RDV + 8) issue_chunk<true>(p, p.fil_off, 2, adv);
     __builtin_amdgcn_sched_barrier(0);
   }
   ring_rotate(p);
@@ -683,12 +708,13 @@ __device__ __forceinline__ void sq_bias_now(const Pipe &p, SqAcc &acc) {
 
 /* directional layer of the split kernel: the plain layer on the split kernel's DMA schedule */
 template <typename MM, int KIND0, int REAL0>
-__device__ __forceinline__ void dir_layer(Pipe &p, typename MM::v8 (&a)[AF], int second, const v4uu (&in)[16], const v4uu (&bn)[8], v4uu (&out)[16]) {
+__device__ __forceinline__ void dir_layer(Pipe &p, typename MM::v8 (&a)[AF], int second, const v4uu (&in)[16], const v4uu (&bn)[8], v4uu (&out)[16], int adv6 = BF_CHUNK_BYTES) {
+  /* `adv6`: what the stream position moves on by behind slice 6 (the last layer of a pass: the stream, two chunks ahead, ends the pass there) */
   /* (pipelining this plain epilogue into the next slice as in sq_layer measured no gain: 105.6 k -> 104.6 k cycles) */
 #pragma unroll
   for (int ob = 0; ob < 8; ++ob) {
     v16f acc;
-    bf_chunk<MM, KIND0, REAL0, true, true>(p, a, in, bn, acc);
+    bf_chunk<MM, KIND0, REAL0, true, true>(p, a, in, bn, acc, NoHook(), ob == 6 ? adv6 : BF_CHUNK_BYTES);
     if constexpr (KIND0 == BF_REG) {
       if (second == 2) bf_chunk<MM, BF_BNLDS, BF_DIR_REAL_KS, false, true>(p, a, in, bn, acc);
     }
@@ -727,16 +753,13 @@ __device__ __forceinline__ void level_fwd_split(const LevelArgs &A) {
   const int col = wave * 32 + n;                             /* this lane's sample column (directional phase) */
 
   Pipe p;
-  p.src = reinterpret_cast<const char *>(A.packed) + wave * 3072 + lane * 16;
-  p.src_end = nullptr;
+  pipe_stream_init(p, A.packed, n_pass * SPPACKED.chunks_per_pass, wave, lane);
   p.wbuf = WB;
   p.xp = Xb + (h * BT + col) * 16;
   /* IPE planes of a run: [k-group][plane (hi | lo)][128 columns = wave * 16 + sample][16 B].  Lane (b = lane / 16, n = lane % 16)
    * reads k-group 4 s + b of k-step s: hi plane, the lo plane (BT / 2) * 16 bytes behind */
   p.xps = Xb + ((lane >> 4) * BT + wave * 16 + (lane & 15)) * 16;
-  p.seq = 0;
   p.cur_off = 0; p.nxt_off = BF_CHUNK_BYTES; p.fil_off = 2 * BF_CHUNK_BYTES;
-  p.dma_left = n_pass * SPPACKED.chunks_per_pass;
   p.lane = lane; p.wave = wave; p.h = h;
   p.t_vm = 0; p.t_bar = 0;
   RN_STAMPW(A, 0);
@@ -778,6 +801,7 @@ __device__ __forceinline__ void level_fwd_split(const LevelArgs &A) {
   for (int pass0 = 0; pass0 < n_tot; pass0 += BT) {
     int lane_v = lane;
     asm volatile("" : "+v"(lane_v));
+    p.lane_off = (unsigned)(wave * 3072 + lane_v * 16);      /* the DMA's lane offset: formed per pass like every lane constant */
     /* which (ray, sample) this lane's column is: recomputed where it is needed (P4, P6) from laundered inputs instead of
      * being carried -- spilled -- across the two spatial runs */
     auto locate = [&](int &g, int &rl, bool &valid) {
@@ -837,7 +861,8 @@ __device__ __forceinline__ void level_fwd_split(const LevelArgs &A) {
       for (int ob = 0; ob < 5; ++ob) {
         SqAcc &acc = ha[(ob + 1) & 1];
         if (ob < 4) {
-          sq_chunk<SQ_BN, true>(p, ar, R1, acc, ha[ob & 1]);
+          /* the stream is two chunks ahead: behind head chunk 2 of run 0 it has fetched the section's last chunk and starts run 1 */
+          sq_chunk<SQ_BN, true>(p, ar, R1, acc, ha[ob & 1], NoHook(), (run == 0 && ob == 2) ? SP_ADV_REWIND : BF_CHUNK_BYTES);
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
             const unsigned pk = e == 0 ? pk_f16(acc.t0[0], acc.t0[1]) : (e == 1 ? pk_f16(acc.t0[2], acc.t0[3])
@@ -970,7 +995,7 @@ __device__ __forceinline__ void level_fwd_split(const LevelArgs &A) {
     RN_STAMPW(A, 12);
 #pragma unroll 1
     for (int it = 0; it < 4; ++it) {
-      dir_layer<MM, BF_REG, 0>(p, ad, (it == 2) ? 2 : 0, R0, bn, R1);
+      dir_layer<MM, BF_REG, 0>(p, ad, (it == 2) ? 2 : 0, R0, bn, R1, it == 3 ? SP_ADV_WRAP : BF_CHUNK_BYTES);
       if (it < 3) dir_layer<MM, BF_REG, 0>(p, ad, 0, R1, bn, R0);
     }
     RN_STAMPW(A, 13);
