@@ -431,6 +431,66 @@ int refnerf_losses_backward(int32_t R, int32_t N, const float *d_r_rgb, const fl
                             float g_data, float g_orientation, float g_normal, const float *d_upstream,
                             float *d_g_r_rgb, float *d_g_weights, float *d_g_normals_pred, void *stream);
 
+/* The six geometry regularisers of one level, fused (internal/train_utils.py:207-279 noisy_consistency_loss, :282-310
+ * noisy_distance_consistency_loss, :313-316 accumulated_weights_loss, :318-329 weights_entropy_loss): one pass each way
+ * instead of a chain of small ATen ops per term whose masked means (x[mask].mean()) are boolean indexings, i.e. a
+ * nonzero and a host synchronisation each.  R rays of S samples; the first n rays have `a` perturbed copies each, the
+ * copy (r, j) being noisy ray r * a + j (the reference reshapes its angle-major noisy batch with reshape(n, a): that
+ * pairing is part of the contract).
+ * refnerf_ray_regularisers_forward writes per-ray rows d_terms [R,8]:
+ *   0  sum_i -w_i log(w_i + 1e-10) where acc > thr_entropy, else 0          1  that mask as 1.0 / 0
+ *   2  (1 - acc)^2
+ *   3..6  diffuse, specular, normal and distance consistency of ray r with its copies where r < n and
+ *         acc > thr_consistency, else 0                                      7  that mask as 1.0 / 0
+ * The caller sums the rows over the rays and forms sum / count * multiplier on the device (an empty mask gives
+ * 0 / 0 = NaN, as mean() of an empty selection does).  Colour measures (REFNERF_CONSISTENCY_*): MSE
+ * sum_c mean_j (x_c - y_jc)^2; AVG_MSE sum_c (x_c - mean_j y_jc)^2; VAR mean_c of the unbiased variance of the a + 1
+ * values.  The specular term's sign flip is the caller's.  Normal: mean_j (1 - n . n_j) on the rendered normals of the
+ * caller's target.  Distance (MSE only): sum_c mean_j ((o + d dist) - (o_j + d_j dist_j))_c^2.
+ * refnerf_ray_regularisers_backward writes dL/d weights [R,S], dL/d acc [R] and, per consistency term, the gradient rows
+ * of the clean side ([R, .]; zero past n) and of the noisy side ([n a, .]), given d_sums = the column sums of d_terms
+ * (float[8]: the counts) and d_scales = float[6] { entropy, acc, diffuse, specular, normal, distance }: multiplier x
+ * warm-up x upstream gradient of each term -- both on the device, so nothing is read back.  Masks carry no gradient;
+ * rays outside a mask get exact zeros.
+ * A term is ON when its pointers are given and costs nothing when they are NULL: entropy d_weights (and d_g_weights),
+ * diffuse / specular / normal the clean and the noisy tensor, distance those two and the four ray tensors.  Mandatory:
+ * d_acc and d_terms (forward) / d_sums and d_scales (backward).  REFNERF_EINVAL: a null mandatory pointer or a term given
+ * in part, R <= 0, S <= 0, n < 0, n > R, n > 0 with a <= 0, an unknown type. */
+enum { REFNERF_CONSISTENCY_MSE = 0, REFNERF_CONSISTENCY_AVG_MSE = 1, REFNERF_CONSISTENCY_VAR = 2 };
+typedef struct refnerf_regularisers_args {
+  int32_t R, S, n, a;
+  float thr_entropy, thr_consistency;          /* Config.acc_threshold_for_weights_entropy_loss / _for_consistency_loss */
+  int32_t diffuse_type, specular_type, distance_type;   /* REFNERF_CONSISTENCY_*; distance: MSE only */
+  const float *d_weights;                      /* [R,S] ray_history['weights'] */
+  const float *d_acc;                          /* [R]   renderings['acc'] */
+  const float *d_distance, *d_diffuse, *d_specular, *d_normals;           /* clean renderings: [R], [R,3] x 3 */
+  const float *d_n_distance, *d_n_diffuse, *d_n_specular, *d_n_normals;   /* noisy renderings: [n a], [n a,3] x 3 */
+  const float *d_origins, *d_directions;       /* [R,3] clean rays (distance term) */
+  const float *d_n_origins, *d_n_directions;   /* [n a,3] noisy rays */
+  float *d_terms;                              /* forward: [R,8] */
+  const float *d_sums, *d_scales;              /* backward: float[8], float[6] */
+  float *d_g_weights, *d_g_acc;                /* backward: [R,S], [R] */
+  float *d_g_distance, *d_g_diffuse, *d_g_specular, *d_g_normals;         /* [R], [R,3] x 3 */
+  float *d_g_n_distance, *d_g_n_diffuse, *d_g_n_specular, *d_g_n_normals; /* [n a], [n a,3] x 3 */
+} refnerf_regularisers_args;
+int refnerf_ray_regularisers_forward(const refnerf_regularisers_args *args, void *stream);
+int refnerf_ray_regularisers_backward(const refnerf_regularisers_args *args, void *stream);
+
+/* The perturbed rays of the consistency terms (internal/sample_utils.py:40-79 sample_noisy_rays) in one launch instead of
+ * a Python loop over the rotations: output ray k = j n + i (angle-major) is ray i seen from rotation j,
+ * directions' = T_j d_i, viewdirs' = T_j v_i, origins' = o_i + dist_i d_i - dist_i directions'; the other six fields are
+ * copied from ray i.  d_rotations [a,3,3] row-major (the caller draws the Euler angles); d_distance [n]; inputs [n, .]
+ * (the first n rays of the batch), outputs [a n, .] with the widths of the Rays fields: origins / directions / viewdirs
+ * 3, imageplane 2, the others 1.  REFNERF_EINVAL: a null pointer, n <= 0 or a <= 0. */
+typedef struct refnerf_noisy_rays_args {
+  int32_t n, a;
+  const float *d_rotations, *d_distance;
+  const float *d_origins, *d_directions, *d_viewdirs, *d_radii, *d_imageplane, *d_lossmult, *d_near, *d_far, *d_cam_idx;
+  float *d_out_origins, *d_out_directions, *d_out_viewdirs, *d_out_radii, *d_out_imageplane, *d_out_lossmult, *d_out_near,
+        *d_out_far, *d_out_cam_idx;
+} refnerf_noisy_rays_args;
+int refnerf_noisy_rays(const refnerf_noisy_rays_args *args, void *stream);
+
 /* The optimiser step of the reference's loop, fused (nerf_system.py:205-217 configure_gradient_clipping +
  * on_after_backward, torch.optim.Adam.step): clip_grad_value_(grad_max_val), clip_grad_norm_(grad_max_norm) over ALL
  * tensors of the step, Adam (no AMSGrad, no weight decay), and the per-segment statistics grad_norm = |g|_2 and

@@ -77,6 +77,29 @@ class AdamCfg(C.Structure):
                                           "grad_max_val")] + [("write_grad", C.c_int32), ("no_step", C.c_int32)]
 
 
+CONSISTENCY_TYPES = {"mse": 0, "avg_mse": 1, "var": 2}   # REFNERF_CONSISTENCY_*
+
+
+class RegularisersArgs(C.Structure):
+    """refnerf_regularisers_args: sizes, thresholds and type enums, then the device pointers of one level (None = term off)."""
+    _fields_ = [(n, C.c_int32) for n in ("R", "S", "n", "a")] + [("thr_entropy", C.c_float), ("thr_consistency", C.c_float)] + [
+        (n, C.c_int32) for n in ("diffuse_type", "specular_type", "distance_type")] + [(n, _FP) for n in (
+            "d_weights", "d_acc", "d_distance", "d_diffuse", "d_specular", "d_normals", "d_n_distance", "d_n_diffuse",
+            "d_n_specular", "d_n_normals", "d_origins", "d_directions", "d_n_origins", "d_n_directions", "d_terms", "d_sums",
+            "d_scales", "d_g_weights", "d_g_acc", "d_g_distance", "d_g_diffuse", "d_g_specular", "d_g_normals",
+            "d_g_n_distance", "d_g_n_diffuse", "d_g_n_specular", "d_g_n_normals")]
+
+
+RAY_FIELDS = ("origins", "directions", "viewdirs", "radii", "imageplane", "lossmult", "near", "far", "cam_idx")   # utils.Rays
+RAY_FIELD_WIDTHS = (3, 3, 3, 1, 2, 1, 1, 1, 1)
+
+
+class NoisyRaysArgs(C.Structure):
+    """refnerf_noisy_rays_args."""
+    _fields_ = [("n", C.c_int32), ("a", C.c_int32), ("d_rotations", _FP), ("d_distance", _FP)] + [
+        ("d_" + n, _FP) for n in RAY_FIELDS] + [("d_out_" + n, _FP) for n in RAY_FIELDS]
+
+
 class HipLibraryError(RuntimeError):
     pass
 
@@ -137,6 +160,9 @@ def lib():
         L.refnerf_render_rays.argtypes = [C.POINTER(LevelCfg), C.c_int32] + [_FP] * 11 + [C.POINTER(LevelOut), _FP]
         L.refnerf_losses_forward.argtypes = [C.c_int32, C.c_int32] + [_FP] * 9 + [_FP]
         L.refnerf_losses_backward.argtypes = [C.c_int32, C.c_int32] + [_FP] * 5 + [C.c_int32] + [_FP] * 3 + [C.c_float] * 3 + [_FP] * 4 + [_FP]
+        L.refnerf_ray_regularisers_forward.argtypes = [C.POINTER(RegularisersArgs), _FP]
+        L.refnerf_ray_regularisers_backward.argtypes = [C.POINTER(RegularisersArgs), _FP]
+        L.refnerf_noisy_rays.argtypes = [C.POINTER(NoisyRaysArgs), _FP]
         L.refnerf_optim_workspace_bytes.restype = C.c_size_t
         L.refnerf_optim_workspace_bytes.argtypes = [C.c_int64, C.c_int32]
         L.refnerf_optim_state_bytes.restype = C.c_size_t
@@ -449,6 +475,94 @@ def losses_backward(r_rgb, gt_rgb, lossmult, weights, orientation_normals, orien
                                         float(g_data), float(g_orientation), float(g_normal), ptr(upstream),
                                         ptr(g_rgb), ptr(g_w), ptr(g_np), stream_ptr()))
     return g_rgb, g_w, g_np
+
+
+_REG_CLEAN = (("distance", 1), ("diffuse", 3), ("specular", 3), ("normals", 3))   # per-ray tensors of a consistency term, widths
+
+
+def regularisers_args(weights, acc, clean, noisy, rays, noisy_rays, n, a, thr_entropy, thr_consistency, types):
+    """(RegularisersArgs, R, S) over contiguous float32 device tensors, every shape checked here (the kernels trust them):
+    weights [R,S] or None; acc [R]; clean / noisy: dicts distance [R] / [n a] and diffuse, specular, normals [R,3] / [n a,3],
+    a missing or None entry = term off; rays / noisy_rays: (origins, directions) [R,3] / [n a,3], needed by the distance
+    term; types: the three REFNERF_CONSISTENCY_* (diffuse, specular, distance)."""
+    dev = acc.device
+
+    def p(t, shape, what):
+        if t is None:
+            return None
+        if not (t.is_cuda and t.device == dev and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape):
+            raise ValueError(f"ray regularisers: {what} must be a contiguous float32 tensor of shape {shape} on {dev}")
+        return t.data_ptr()
+    R = acc.shape[0]
+    S = weights.shape[1] if weights is not None else 1
+    A = RegularisersArgs()
+    A.R, A.S, A.n, A.a = int(R), int(S), int(n), int(a)
+    A.thr_entropy, A.thr_consistency = float(thr_entropy), float(thr_consistency)
+    A.diffuse_type, A.specular_type, A.distance_type = (int(t) for t in types)
+    # (sizes the library refuses are left to its message; the shapes below are then checked against clamped ones)
+    na = max(int(n), 0) * max(int(a), 0)
+    A.d_weights, A.d_acc = p(weights, (R, S), "weights"), p(acc, (R,), "acc")
+    for k, w in _REG_CLEAN:
+        setattr(A, "d_" + k, p(clean.get(k), (R,) if w == 1 else (R, w), k))
+        setattr(A, "d_n_" + k, p(noisy.get(k), (na,) if w == 1 else (na, w), "noisy " + k))
+    if clean.get("distance") is not None:
+        A.d_origins, A.d_directions = p(rays[0], (R, 3), "origins"), p(rays[1], (R, 3), "directions")
+        A.d_n_origins, A.d_n_directions = p(noisy_rays[0], (na, 3), "noisy origins"), p(noisy_rays[1], (na, 3), "noisy directions")
+    return A, R, S
+
+
+def ray_regularisers_forward(A: RegularisersArgs, device):
+    """refnerf_ray_regularisers_forward on the arguments of regularisers_args -> terms [R,8] (see include/refnerf_hip.h)."""
+    require_device()
+    terms = torch.empty((max(int(A.R), 1), 8), dtype=torch.float32, device=device)
+    A.d_terms = terms.data_ptr()
+    check(lib().refnerf_ray_regularisers_forward(C.byref(A), stream_ptr()))
+    return terms
+
+
+def ray_regularisers_backward(A: RegularisersArgs, sums, scales):
+    """refnerf_ray_regularisers_backward: sums float[8] (the forward's column sums), scales float[6] (multiplier x warm-up x
+    upstream of entropy, acc, diffuse, specular, normal, distance), both on the device.  Returns dict(weights, acc, distance,
+    diffuse, specular, normals, n_distance, ...) of the gradients of the terms that are on (the others None)."""
+    require_device()
+    if not (sums.is_cuda and sums.dtype == torch.float32 and sums.is_contiguous() and sums.numel() == 8 and
+            scales.is_cuda and scales.dtype == torch.float32 and scales.is_contiguous() and scales.numel() == 6):
+        raise ValueError("ray regularisers: sums / scales must be contiguous float32 device tensors of 8 / 6 elements")
+    f32 = dict(dtype=torch.float32, device=sums.device)
+    R, S, na = max(int(A.R), 1), max(int(A.S), 1), max(int(A.n), 0) * max(int(A.a), 0)
+    out = {"weights": torch.empty((R, S), **f32) if A.d_weights else None, "acc": torch.empty((R,), **f32)}
+    for k, w in _REG_CLEAN:
+        on = bool(getattr(A, "d_" + k))
+        out[k] = torch.empty((R,) if w == 1 else (R, w), **f32) if on else None
+        out["n_" + k] = torch.empty((na,) if w == 1 else (na, w), **f32) if on else None
+    for k, t in out.items():
+        setattr(A, "d_g_" + k, None if t is None else t.data_ptr())
+    A.d_sums, A.d_scales = sums.data_ptr(), scales.data_ptr()
+    check(lib().refnerf_ray_regularisers_backward(C.byref(A), stream_ptr()))
+    return out
+
+
+def noisy_rays(rotations, distance, fields):
+    """refnerf_noisy_rays: rotations [a,3,3], distance [n], fields: the nine utils.Rays tensors [n, w] in RAY_FIELDS order
+    (contiguous float32 device tensors) -> the nine [a n, w] tensors of the perturbed rays, angle-major."""
+    require_device()
+    dev = distance.device
+    a, n = int(rotations.shape[0]), int(distance.shape[0])
+    A = NoisyRaysArgs()
+    A.n, A.a = n, a
+
+    def p(t, shape, what):
+        if not (t.is_cuda and t.device == dev and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape):
+            raise ValueError(f"noisy_rays: {what} must be a contiguous float32 tensor of shape {shape} on {dev}")
+        return t.data_ptr()
+    A.d_rotations, A.d_distance = p(rotations, (a, 3, 3), "rotations"), p(distance, (n,), "distance")
+    outs = []
+    for name, w, t in zip(RAY_FIELDS, RAY_FIELD_WIDTHS, fields):
+        setattr(A, "d_" + name, p(t, (n, w), name))
+        outs.append(torch.empty((a * n, w), dtype=torch.float32, device=dev))
+        setattr(A, "d_out_" + name, outs[-1].data_ptr())
+    check(lib().refnerf_noisy_rays(C.byref(A), stream_ptr()))
+    return outs
 
 
 def _ptr32(t):

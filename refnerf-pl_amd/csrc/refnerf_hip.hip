@@ -31,6 +31,7 @@
 #include "refnerf_wgrad_bf16x3.h"
 #include "refnerf_rays.h"
 #include "refnerf_optim.h"
+#include "refnerf_regularisers.h"
 #include "refnerf_pack_common.h"
 #include "refnerf_sq_host.h"
 #include "refnerf_sq_layout.h"
@@ -1228,6 +1229,68 @@ int refnerf_losses_backward(int32_t R, int32_t N, const float *d_r_rgb, const fl
   a.g_rgb = d_g_r_rgb; a.g_weights = d_g_weights; a.g_npred = d_g_normals_pred;
   const size_t n = (size_t)R * N;
   hipLaunchKernelGGL(rn::refnerf_losses_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+  HIP_TRY(hipGetLastError());
+  return REFNERF_OK;
+}
+
+/* ---- the six geometry regularisers and the perturbed-ray sampler (refnerf_regularisers.h) ---- */
+namespace {
+static int check_regularisers(const refnerf_regularisers_args *a, const char *fn) {
+  if (!a || !a->d_acc) return fail(REFNERF_EINVAL, "%s: null pointer", fn);
+  if (a->R <= 0 || a->S <= 0) return fail(REFNERF_EINVAL, "%s: R and S must be positive", fn);
+  if (a->n < 0 || a->n > a->R) return fail(REFNERF_EINVAL, "%s: n must be in [0, R]", fn);
+  if (a->n > 0 && a->a <= 0) return fail(REFNERF_EINVAL, "%s: a must be positive when n > 0", fn);
+  for (int t : {a->diffuse_type, a->specular_type})
+    if (t != REFNERF_CONSISTENCY_MSE && t != REFNERF_CONSISTENCY_AVG_MSE && t != REFNERF_CONSISTENCY_VAR)
+      return fail(REFNERF_EINVAL, "%s: unknown consistency loss type (REFNERF_CONSISTENCY_*)", fn);
+  if (a->distance_type != REFNERF_CONSISTENCY_MSE)
+    return fail(REFNERF_EINVAL, "%s: the distance consistency type must be REFNERF_CONSISTENCY_MSE", fn);
+  /* a term is given whole (clean and noisy side; the distance term with the four ray tensors) or not at all */
+  if (!a->d_diffuse != !a->d_n_diffuse || !a->d_specular != !a->d_n_specular || !a->d_normals != !a->d_n_normals ||
+      !a->d_distance != !a->d_n_distance ||
+      (a->d_distance && (!a->d_origins || !a->d_directions || !a->d_n_origins || !a->d_n_directions)))
+    return fail(REFNERF_EINVAL, "%s: a consistency term needs its clean and its noisy tensors (distance: the rays as well)", fn);
+  return REFNERF_OK;
+}
+}  // namespace
+
+int refnerf_ray_regularisers_forward(const refnerf_regularisers_args *args, void *stream) {
+  if (int rc = check_regularisers(args, "refnerf_ray_regularisers_forward")) return rc;
+  if (!args->d_terms) return fail(REFNERF_EINVAL, "refnerf_ray_regularisers_forward: null pointer%s");
+  hipLaunchKernelGGL(rn::ray_regularisers_fwd_kernel, dim3((args->R + 3) / 4), dim3(256), 0, (hipStream_t)stream, *args);
+  HIP_TRY(hipGetLastError());
+  return REFNERF_OK;
+}
+
+int refnerf_ray_regularisers_backward(const refnerf_regularisers_args *args, void *stream) {
+  const char *fn = "refnerf_ray_regularisers_backward";
+  if (int rc = check_regularisers(args, fn)) return rc;
+  if (!args->d_sums || !args->d_scales) return fail(REFNERF_EINVAL, "%s: null pointer", fn);
+  if (args->d_g_weights && !args->d_weights) return fail(REFNERF_EINVAL, "%s: d_g_weights without d_weights", fn);
+  /* a gradient is written for a term that is on, to both sides */
+  if ((args->d_g_diffuse && !args->d_diffuse) || (args->d_g_specular && !args->d_specular) ||
+      (args->d_g_normals && !args->d_normals) || (args->d_g_distance && !args->d_distance) ||
+      !args->d_g_diffuse != !args->d_g_n_diffuse || !args->d_g_specular != !args->d_g_n_specular ||
+      !args->d_g_normals != !args->d_g_n_normals || !args->d_g_distance != !args->d_g_n_distance)
+    return fail(REFNERF_EINVAL, "%s: a consistency term's gradient needs the term's inputs and both output tensors", fn);
+  const size_t n = args->d_g_weights ? (size_t)args->R * args->S : (size_t)args->R;
+  hipLaunchKernelGGL(rn::ray_regularisers_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *args);
+  HIP_TRY(hipGetLastError());
+  return REFNERF_OK;
+}
+
+int refnerf_noisy_rays(const refnerf_noisy_rays_args *args, void *stream) {
+  if (!args) return fail(REFNERF_EINVAL, "refnerf_noisy_rays: null pointer%s");
+  const void *ptrs[] = {args->d_rotations, args->d_distance, args->d_origins, args->d_directions, args->d_viewdirs, args->d_radii,
+                        args->d_imageplane, args->d_lossmult, args->d_near, args->d_far, args->d_cam_idx, args->d_out_origins,
+                        args->d_out_directions, args->d_out_viewdirs, args->d_out_radii, args->d_out_imageplane, args->d_out_lossmult,
+                        args->d_out_near, args->d_out_far, args->d_out_cam_idx};
+  for (const void *p : ptrs)
+    if (!p) return fail(REFNERF_EINVAL, "refnerf_noisy_rays: null pointer%s");
+  if (args->n <= 0 || args->a <= 0) return fail(REFNERF_EINVAL, "refnerf_noisy_rays: n and a must be positive%s");
+  const size_t total = (size_t)args->n * args->a;
+  if (total > (size_t)INT32_MAX) return fail(REFNERF_EINVAL, "refnerf_noisy_rays: n * a must be below 2^31%s");
+  hipLaunchKernelGGL(rn::noisy_rays_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *args);
   HIP_TRY(hipGetLastError());
   return REFNERF_OK;
 }

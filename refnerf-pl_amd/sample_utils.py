@@ -32,8 +32,11 @@ def euler_angles_to_matrix(euler_angles: torch.Tensor) -> torch.Tensor:
 @torch.no_grad()
 def sample_noisy_rays(rays: utils.Rays, rendering: dict, sample_angle_range: float = 0.,
                       sample_noise_size: int = 128, sample_noise_angles: int = 1,
-                      warmup_ratio: float = 1., rotations=None) -> utils.Rays:
-    """sample_utils.py:40-79.  `rotations` ([angles,3,3]) overrides the random draw (tests)."""
+                      warmup_ratio: float = 1., rotations=None, fused: bool = False) -> utils.Rays:
+    """sample_utils.py:40-79.  `rotations` ([angles,3,3]) overrides the random draw (tests).  `fused`
+    (Config.hip_fused_regularisers): on a flat batch of device tensors the nine fields come from ONE launch of
+    refnerf_noisy_rays instead of the cat / matmul loop over the rotations below (same dtypes, shapes and values); the
+    Euler-angle draw and euler_angles_to_matrix stay in torch."""
     dev = rendering['distance'].device
     if rotations is None:
         hi = sample_angle_range / 180 * math.pi * warmup_ratio
@@ -52,6 +55,11 @@ def sample_noisy_rays(rays: utils.Rays, rendering: dict, sample_angle_range: flo
         distance = distance[..., None]
     elif distance.dim() != f32(rays.origins).dim():
         raise ValueError('The dimension of distance is wrong.')
+    if fused and distance.is_cuda and distance.dim() == 2 and n > 0 and sample_noise_angles > 0:
+        from . import _hip
+        fields = [f32(getattr(rays, k))[:n].contiguous() for k in _hip.RAY_FIELDS]
+        return utils.Rays(**dict(zip(_hip.RAY_FIELDS, _hip.noisy_rays(
+            rotations.contiguous(), distance[:n].to(torch.float32).reshape(n).contiguous(), fields))))
     distance = torch.cat([distance[:n]] * sample_noise_angles)
     viewdirs_ = torch.cat([f32(rays.viewdirs)[:n] @ T.T for T in rotations])
     directions_ = torch.cat([f32(rays.directions)[:n] @ T.T for T in rotations])

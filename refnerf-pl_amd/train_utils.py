@@ -216,6 +216,133 @@ def interlevel_loss(ray_history, config):
     return config.interlevel_loss_mult * total
 
 
+_REG_TERMS = ('weights_entropy', 'acc', 'diffuse_consistency', 'specular_consistency', 'normals_consistency',
+              'distance_consistency')        # the order of the kernels' scales / of the node's per-term output
+_REG_INPUTS = ('weights', 'acc', 'distance', 'diffuse', 'specular', 'normals')
+
+
+class _FusedRayRegularisers(torch.autograd.Function):
+    """The six geometry regularisers of ONE level (weights entropy, accumulated weights, diffuse / specular / normal /
+    distance consistency) as a single autograd node on refnerf_ray_regularisers_forward / _backward
+    (Config.hip_fused_regularisers): what noisy_consistency_loss, noisy_distance_consistency_loss, accumulated_weights_loss
+    and weights_entropy_loss compute with a chain of ATen ops and boolean indexings per term, in one pass each way and
+    without a host synchronisation.  Inputs that are None switch their term off.  Returns (per_term [6] in _REG_TERMS
+    order, multipliers and warm-up applied; sums [8], the kernel's column sums)."""
+
+    @staticmethod
+    def forward(ctx, aux, weights, acc, distance, diffuse, specular, normals, n_distance, n_diffuse, n_specular, n_normals):
+        from . import _hip
+        R, na = acc.shape[0], aux['n'] * aux['a']
+        ins = (weights, acc, distance, diffuse, specular, normals, n_distance, n_diffuse, n_specular, n_normals)
+
+        def flat(t, rows, width):
+            if t is None:
+                return None
+            return t.detach().to(torch.float32).reshape((rows,) if width == 1 else (rows, width)).contiguous()
+        w_c = None if weights is None else weights.detach().to(torch.float32).reshape(R, -1).contiguous()
+        clean = dict(zip(_REG_INPUTS[2:], (flat(t, R, w) for t, w in zip(ins[2:6], (1, 3, 3, 3)))))
+        noisy = dict(zip(_REG_INPUTS[2:], (flat(t, na, w) for t, w in zip(ins[6:], (1, 3, 3, 3)))))
+        acc_c = flat(acc, R, 1)
+        args, _, _ = _hip.regularisers_args(w_c, acc_c, clean, noisy, aux['rays'], aux['noisy_rays'], aux['n'], aux['a'],
+                                            aux['thr_entropy'], aux['thr_consistency'], aux['types'])
+        sums = _hip.ray_regularisers_forward(args, acc.device).sum(dim=0)
+        ctx.set_materialize_grads(False)
+        ctx.aux, ctx.args, ctx.shapes = aux, args, [None if t is None else t.shape for t in ins]
+        ctx.keep = (w_c, acc_c, clean, noisy)                # the tensors behind the argument struct's pointers
+        consts = aux['consts']                        # device float[7]: the six scales, then the ray count
+        values = torch.cat([sums[0:1], sums[2:7]])
+        counts = torch.cat([sums[1:2], consts[6:7], sums[7:8].expand(4)])
+        per_term = values / counts * consts[:6]
+        ctx.sums = sums
+        ctx.mark_non_differentiable(sums)
+        return per_term, sums
+
+    @staticmethod
+    def backward(ctx, g_terms, _g_sums):
+        from . import _hip
+        if g_terms is None:
+            return (None,) * 11
+        # upstream gradient of the six terms times multiplier and warm-up, on the device (no host sync)
+        up = (g_terms.to(torch.float32) * ctx.aux['consts'][:6]).contiguous()
+        g = _hip.ray_regularisers_backward(ctx.args, ctx.sums, up)
+        names = _REG_INPUTS + tuple('n_' + k for k in _REG_INPUTS[2:])
+        return (None,) + tuple(None if shape is None or g[k] is None else g[k].reshape(shape)
+                               for k, shape in zip(names, ctx.shapes))
+
+
+def fused_regularisers_supported(config):
+    """The fused path covers what the ATen functions accept: the three colour measures, the 'mse' distance measure and the
+    two normal targets (anything else keeps the ATen path and its ValueError)."""
+    from . import _hip
+    return (config.consistency_diffuse_loss_type in _hip.CONSISTENCY_TYPES and
+            config.consistency_specular_loss_type in _hip.CONSISTENCY_TYPES and
+            config.consistency_distance_loss_type == 'mse' and
+            config.consistency_normal_loss_target in ('normals', 'normals_pred'))
+
+
+def fused_ray_regularisers(model, rays, noisy_rays, renderings, renderings_noise, ray_history, config, warmup_ratio=1.):
+    """noisy_consistency_loss + noisy_distance_consistency_loss + accumulated_weights_loss + weights_entropy_loss
+    (train_utils.py:207-329) through the fused kernels, one autograd node per level: returns a dict with those of
+    'diffuse_consistency', 'specular_consistency', 'normals_consistency', 'acc', 'distance_consistency' and
+    'weights_entropy' that Config switches on, with the same values (fp32 summation order aside) and the same gradients into
+    the clean and the noisy renderings and ray_history['weights'].  Flat batches ([R, .] rays) on the device; nothing is
+    read back to the host.  Depth smoothness (patch batches) and the interlevel loss stay ATen."""
+    from . import _hip
+    dev = renderings[0]['acc'].device
+    f32 = dict(dtype=torch.float32, device=dev)
+    want_c = wants_noisy_pass(config)
+    want_d = _any_positive(config, 'consistency_distance_loss_mult', 'consistency_distance_coarse_loss_mult')
+    want_e = _any_positive(config, 'weights_entropy_loss_mult', 'weights_entropy_coarse_loss_mult')
+    want_a = config.accumulated_weights_loss_mult > 0
+    if (want_c or want_d) and renderings_noise is None:
+        raise ValueError('the consistency losses need the renderings of the noisy rays (training_losses)')
+    if want_d and noisy_rays is None:
+        raise ValueError('the distance consistency loss needs the noisy rays and their renderings')
+    n = config.sample_noise_size // config.patch_size ** 2 if (want_c or want_d) else 0
+    a = config.sample_noise_angles if n > 0 else 0
+    target = config.consistency_normal_loss_target
+    L = len(renderings)
+    rows = []
+    for i in range(L):
+        def mult(name):
+            fine = getattr(config, f'{name}_loss_mult')
+            return fine if i >= model.num_levels - 1 else getattr(config, f'{name}_coarse_loss_mult')
+        rows.append([warmup_ratio * mult('weights_entropy'),
+                     config.accumulated_weights_loss_mult if i == L - 1 else 0.,
+                     warmup_ratio * mult('consistency_diffuse'), -warmup_ratio * mult('consistency_specular'),
+                     warmup_ratio * mult('consistency_normal'), warmup_ratio * mult('consistency_distance'),
+                     float(renderings[i]['acc'].shape[0])])
+    # one asynchronous upload per step: per level the six scales (multiplier x warm-up; the specular term is maximised) and R
+    consts = torch.tensor(rows, dtype=torch.float32).pin_memory().to(dev, non_blocking=True)
+    ray_pair = noisy_pair = None
+    if want_d:
+        ray_pair = tuple(torch.as_tensor(x, **f32).reshape(-1, 3).contiguous() for x in (rays.origins, rays.directions))
+        noisy_pair = tuple(torch.as_tensor(x, **f32).reshape(-1, 3).contiguous() for x in (noisy_rays.origins, noisy_rays.directions))
+    per_level = []
+    for i, (clean, hist) in enumerate(zip(renderings, ray_history)):
+        noisy = renderings_noise[i] if (want_c or want_d) else {}
+        if want_c:
+            if clean.get('normals') is None or clean.get('normals_pred') is None:
+                raise ValueError('Predicted normals and gradient normals cannot be None if consistency loss is on.')
+        aux = dict(n=n, a=a, rays=ray_pair, noisy_rays=noisy_pair, consts=consts[i],
+                   thr_entropy=config.acc_threshold_for_weights_entropy_loss,
+                   thr_consistency=config.acc_threshold_for_consistency_loss,
+                   types=(_hip.CONSISTENCY_TYPES[config.consistency_diffuse_loss_type],
+                          _hip.CONSISTENCY_TYPES[config.consistency_specular_loss_type],
+                          _hip.CONSISTENCY_TYPES[config.consistency_distance_loss_type]))
+
+        def pick(src, key, on):
+            return src[key] if on else None
+        per_term, _ = _FusedRayRegularisers.apply(
+            aux, hist['weights'] if want_e else None, clean['acc'],
+            pick(clean, 'distance', want_d), pick(clean, 'diffuse', want_c), pick(clean, 'specular', want_c), pick(clean, target, want_c),
+            pick(noisy, 'distance', want_d), pick(noisy, 'diffuse', want_c), pick(noisy, 'specular', want_c), pick(noisy, target, want_c))
+        per_level.append(per_term)
+    totals = torch.stack(per_level).sum(dim=0)          # coarse levels first, as the reference accumulates
+    on = dict(zip(_REG_TERMS, (want_e, want_a, want_c, want_c, want_c, want_d)))
+    return {k: totals[j] for j, k in enumerate(_REG_TERMS) if on[k]}
+
+
 def _level_mult(i, model, coarse, fine):
     return coarse if i < model.num_levels - 1 else fine
 
@@ -369,7 +496,7 @@ def training_losses(model, batch, rays, config, train_frac=1.0, global_step=None
         if noisy_rays is None:
             noisy_rays = sample_utils.sample_noisy_rays(
                 rays, renderings[-1], config.sample_angle_range, config.sample_noise_size // config.patch_size ** 2,
-                config.sample_noise_angles, ratio)
+                config.sample_noise_angles, ratio, fused=getattr(config, 'hip_fused_regularisers', False))
         renderings_noise, _ = model(noisy_rays, train_frac, True)
     total, losses, stats = compute_losses(model, batch, rays, renderings, ray_history, config,
                                           renderings_noise=renderings_noise, noisy_rays=noisy_rays, warmup_ratio=ratio)
@@ -380,7 +507,9 @@ def training_losses(model, batch, rays, config, train_frac=1.0, global_step=None
 def compute_losses(model, batch, rays, renderings, ray_history, config, renderings_noise=None, noisy_rays=None,
                    warmup_ratio=1.):
     """The loss assembly of NeRFSystem.training_step (nerf_system.py:118-180) on already computed
-    renderings: returns (total, dict of terms, stats)."""
+    renderings: returns (total, dict of terms, stats).  Config.hip_fused_losses / hip_fused_regularisers route the three Ref-NeRF
+    terms / the six geometry regularisers through their fused kernels (same keys, same order); depth smoothness and the
+    interlevel loss stay ATen."""
     losses = {}
     fused = getattr(config, 'hip_fused_losses', False) and fused_losses_supported(config) and renderings[0]['rgb'].is_cuda
     if fused:      # opt-in: the three Ref-NeRF terms of every level through refnerf_losses_forward / _backward
@@ -396,20 +525,33 @@ def compute_losses(model, batch, rays, renderings, ray_history, config, renderin
         losses['predicted_normals'] = n_loss if fused else predicted_normal_loss(model, ray_history, config)
     if config.patch_size > 1 and _any_positive(config, 'depth_smoothness_coarse_loss_mult', 'depth_smoothness_loss_mult'):
         losses['smoothness'] = compute_depth_smoothness_loss(renderings, config)
+    want_distance = _any_positive(config, 'consistency_distance_loss_mult', 'consistency_distance_coarse_loss_mult')
+    # opt-in: the six geometry regularisers of every level through refnerf_ray_regularisers_forward / _backward (flat batches on
+    # the device; a missing noisy pass falls through to the ATen branches below and their ValueErrors)
+    want_entropy = _any_positive(config, 'weights_entropy_loss_mult', 'weights_entropy_coarse_loss_mult')
+    fused_reg = (getattr(config, 'hip_fused_regularisers', False) and fused_regularisers_supported(config) and
+                 (wants_noisy_pass(config) or want_distance or want_entropy or config.accumulated_weights_loss_mult > 0) and
+                 renderings[0]['acc'].is_cuda and getattr(rays.origins, 'ndim', 0) == 2 and
+                 not ((wants_noisy_pass(config) or want_distance) and renderings_noise is None) and
+                 not (want_distance and noisy_rays is None))
+    reg = fused_ray_regularisers(model, rays, noisy_rays, renderings, renderings_noise, ray_history, config,
+                                 warmup_ratio) if fused_reg else None
     if wants_noisy_pass(config):
         if renderings_noise is None:
             raise ValueError('the consistency losses need the renderings of the noisy rays (training_losses)')
-        (losses['diffuse_consistency'], losses['specular_consistency'],
-         losses['normals_consistency']) = noisy_consistency_loss(model, renderings, renderings_noise, config, warmup_ratio)
+        (losses['diffuse_consistency'], losses['specular_consistency'], losses['normals_consistency']) = (
+            reg['diffuse_consistency'], reg['specular_consistency'], reg['normals_consistency']) if fused_reg else \
+            noisy_consistency_loss(model, renderings, renderings_noise, config, warmup_ratio)
     if config.accumulated_weights_loss_mult > 0:
-        losses['acc'] = accumulated_weights_loss(renderings, config)
-    if _any_positive(config, 'consistency_distance_loss_mult', 'consistency_distance_coarse_loss_mult'):
+        losses['acc'] = reg['acc'] if fused_reg else accumulated_weights_loss(renderings, config)
+    if want_distance:
         if renderings_noise is None or noisy_rays is None:
             raise ValueError('the distance consistency loss needs the noisy rays and their renderings')
-        losses['distance_consistency'] = noisy_distance_consistency_loss(
+        losses['distance_consistency'] = reg['distance_consistency'] if fused_reg else noisy_distance_consistency_loss(
             model, rays, noisy_rays, renderings, renderings_noise, config, warmup_ratio)
-    if _any_positive(config, 'weights_entropy_loss_mult', 'weights_entropy_coarse_loss_mult'):
-        losses['weights_entropy'] = weights_entropy_loss(model, renderings, ray_history, config, warmup_ratio)
+    if want_entropy:
+        losses['weights_entropy'] = reg['weights_entropy'] if fused_reg else \
+            weights_entropy_loss(model, renderings, ray_history, config, warmup_ratio)
     total = torch.sum(torch.stack([torch.as_tensor(v, dtype=torch.float32, device=data_loss.device)
                                    for v in losses.values()]))
     if getattr(config, 'hip_check_finite', True):
