@@ -207,6 +207,15 @@ __device__ __forceinline__ float ipe_feature_split(float lm, float lv, int j, in
   const float e = __builtin_amdgcn_exp2f((-0.5f * LOG2E_F) * (lv * sc2));
   return e * sin_reduced(safe_arg_exact(x));
 }
+/* The same feature from the degree's scales 2^j and 4^j held as floats (a caller whose loop knows the degree where it is
+ * written keeps them as running powers of two instead of forming them per feature from a run-time j): the same two fp32
+ * products lm 2^j and lv 4^j, the same operations behind them -- the same bits as ipe_feature_split(lm, lv, j, cos_block). */
+__device__ __forceinline__ float ipe_feature_split_sc(float lm, float lv, float sc, float sc2, int cos_block) {
+  float x = lm * sc;
+  if (cos_block) x = x + HALF_PI_F;
+  const float e = __builtin_amdgcn_exp2f((-0.5f * LOG2E_F) * (lv * sc2));
+  return e * sin_reduced(safe_arg_exact(x));
+}
 
 /* One IPE feature (coord.py:119-126): block 0 = sin, block 1 = "cos" =
  * sin(fl(x + pi/2)). */

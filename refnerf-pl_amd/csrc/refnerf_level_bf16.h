@@ -593,9 +593,13 @@ __device__ __forceinline__ void split_pair_f16(float x0, float x1, unsigned &hi,
 /* ---- the spatial section on v_mfma_f32_16x16x32_f16: three partial products into one accumulator (refnerf_layout.h) ---- */
 typedef _Float16 sq_v8 __attribute__((ext_vector_type(8)));
 constexpr int SQ_NF = 4;                         /* fragment ring: the four pieces of a k-step */
+/* SQ_X with the B fragments in registers: a chunk of this kind takes the three IPE k-steps from `in` ([H(s) L(s)] x 3, loaded
+ * once per layer: sq_layer) -- the chunk in the image is an SQ_X chunk, the schedule of its MFMAs and pieces the same */
+constexpr int SQ_XR = 11;
+static_assert(SQ_XR != SQ_A && SQ_XR != SQ_B && SQ_XR != SQ_X && SQ_XR != SQ_BN && SQ_XR != SQ_SC, "a kind of its own");
 struct SqAcc { v4f t0, t1; };                    /* the two 16-row tiles of a 32-row slice: lane (b, n) holds rows 4 b .. 4 b + 3 for sample n */
-template <int KIND> constexpr int sq_nm() { return KIND == SQ_X ? 18 : (KIND == SQ_BN ? 32 : 24); }      /* MFMAs of a chunk */
-template <int KIND> constexpr int sq_np() { return KIND == SQ_X ? 12 : 16; }                              /* pieces it consumes */
+template <int KIND> constexpr int sq_nm() { return (KIND == SQ_X || KIND == SQ_XR) ? 18 : (KIND == SQ_BN ? 32 : 24); }      /* MFMAs of a chunk */
+template <int KIND> constexpr int sq_np() { return (KIND == SQ_X || KIND == SQ_XR) ? 12 : 16; }                              /* pieces it consumes */
 /* static schedule of MFMA j of a chunk: k-step, piece, hi / lo input fragment, tile, and the piece whose last use it is.
  * A / B / X, per k-step: [WhT0 H | WhT1 H | WlT0 H | WlT1 H | WhT0 L | WhT1 L] (per accumulator: hi*hi, lo*hi, hi*lo);
  * BN: [WhT0 H | WhT1 H | WhT0 L | WhT1 L];  SC: [WhT0 H | WlT0 H | WhT0 L] */
@@ -676,6 +680,7 @@ __device__ __forceinline__ void sq_epi_piece(const SqAcc &a, int q, v4uu &oh, v4
 }
 /* One spatial layer: slice ob's epilogue rides behind the first MFMAs of slice ob + 1 (all eight waves run the chunks in
  * lockstep: VALU work between two slices idles the matrix pipe of every SIMD) */
+/* LAYER0: `in`[0..5] = the IPE planes' six B fragments (sq_load_ipe_frags), the same for all eight slices */
 template <bool LAYER0>
 __device__ __forceinline__ void sq_layer(Pipe &p, sq_v8 (&fr)[SQ_NF], SqAcc (&accs)[2], bool skip, const v4uu (&in)[16], v4uu (&out)[16]) {
   /* slice ob accumulates in accs[(ob + 1) & 1]: on entry accs[1] holds the bias of slice 0, on exit that of the first slice
@@ -688,7 +693,7 @@ __device__ __forceinline__ void sq_layer(Pipe &p, sq_v8 (&fr)[SQ_NF], SqAcc (&ac
       if (ob == 0 || j >= 8 || (j & 1)) return;
       sq_epi_piece(prev, j >> 1, out[2 * ob - 2], out[2 * ob - 1]);
     };
-    if constexpr (LAYER0) sq_chunk<SQ_X, true>(p, fr, in, acc, prev, hook);
+    if constexpr (LAYER0) sq_chunk<SQ_XR, true>(p, fr, in, acc, prev, hook);
     else {
       sq_chunk<SQ_A, false>(p, fr, in, acc, prev, hook);
       sq_chunk<SQ_B, true>(p, fr, in, acc, prev);
@@ -698,6 +703,17 @@ __device__ __forceinline__ void sq_layer(Pipe &p, sq_v8 (&fr)[SQ_NF], SqAcc (&ac
 #pragma unroll
   for (int q = 0; q < 4; ++q) sq_epi_piece(accs[0], q, out[14], out[15]);
   __builtin_amdgcn_sched_barrier(0);
+}
+/* the six B fragments of layer 0 -- the three IPE k-steps' H and L: 96 features x 16 samples -- from the LDS planes into
+ * in[0..5] as [H(s) L(s)], the order the register kinds of sq_chunk index.  Layer 0 runs eight SQ_X chunks over the same
+ * fragments: read per chunk (as the skip layer does, both register sets live) each read sat behind the lgkmcnt(0) in front
+ * of its k-step's first MFMA, eight times */
+__device__ __forceinline__ void sq_load_ipe_frags(const Pipe &p, v4uu (&in)[16]) {
+#pragma unroll
+  for (int s = 0; s < 3; ++s) {
+    in[2 * s] = __builtin_bit_cast(v4uu, lds_frag<MmF16>(p.xps + s * (4 * BT * 16)));
+    in[2 * s + 1] = __builtin_bit_cast(v4uu, lds_frag<MmF16>(p.xps + s * (4 * BT * 16) + (BT / 2) * 16));
+  }
 }
 /* the bias piece of the chunk in the `cur` slot (the first chunk of a run / of the heads: nothing ran ahead to fetch it) */
 __device__ __forceinline__ void sq_bias_now(const Pipe &p, SqAcc &acc) {
@@ -828,10 +844,11 @@ __device__ __forceinline__ void level_fwd_split(const LevelArgs &A) {
       const int g0 = pass0 + wave * 32;
       if (g0 >= n_tot || ray0 + g0 / N >= A.R) { idle_pass<true>(p); pass_epilogue(); continue; }
     }
-    auto load_heads = [&](SampleHeads &sh) {
+    /* (P4 only: P6 takes what it needs of the activated heads from the sample's record, where P4 parks it) */
+    auto load_heads = [&](SampleHeads &sh, int &g, bool &valid) {
       /* ONE address register for the twelve rows (HD sits past the 64 KB immediate range of the ds instructions: left to
        * itself hipcc keeps a base per row, hoists them out of the pass loop and spills them) */
-      int g, rl; bool valid;
+      int rl;
       locate(g, rl, valid);
       int ci = col, ro = (valid ? rl : 0) * 12;
       asm volatile("" : "+v"(ci), "+v"(ro));
@@ -914,25 +931,32 @@ __device__ __forceinline__ void level_fwd_split(const LevelArgs &A) {
       if (cfg.disable_integration) { lv[0] = 0.0f; lv[1] = 0.0f; lv[2] = 0.0f; }        /* models.py:228-231 */
       char *xw = Xb + (wave * 16 + i16) * 16;
       RN_STAMPW(A, 17);
-      /* two features per trip (one dword of the hi plane, one of the lo plane): the libm sine is long, keep ONE copy pair */
+      /* one degree PAIR per trip: six features kk = 6 dp .. 6 dp + 5 = 3 * (j - 8 qq) + b, i.e. three dwords of the hi plane and
+       * three of the lo plane.  Degree parity and axis of a feature are constants of the body (the 12-trip loop of feature
+       * pairs derived both at run time -- kk / 3, kk % 3, two three-way selects and two ldexp per feature); the pair's scales
+       * 2^j and 4^j run along as exact powers of two, so lm 2^j and lv 4^j stay the single fp32 products they were. */
+      float sc = qq ? 256.0f : 1.0f, sc2 = qq ? 65536.0f : 1.0f;      /* 2^j, 4^j at j = 8 qq */
+      char *xq = xw + (6 * hb + 3 * qq) * BT * 16;
 #pragma clang loop unroll(disable)
-      for (int t = 0; t < 12; ++t) {
-        unsigned whi, wlo;
-        {
+      for (int dp = 0; dp < 4; ++dp) {
+        const float sc_odd = sc * 2.0f, sc2_odd = sc2 * 4.0f;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
           float f[2];
 #pragma unroll
           for (int u = 0; u < 2; ++u) {
-            const int kk = 2 * t + u;                  /* 3 * (j - 8 qq) + b */
-            const int jj = kk / 3, b3 = kk - 3 * jj;
-            const float m = b3 == 0 ? lm[0] : (b3 == 1 ? lm[1] : lm[2]);
-            const float v = b3 == 0 ? lv[0] : (b3 == 1 ? lv[1] : lv[2]);
-            f[u] = ipe_feature_split(m, v, 8 * qq + jj, hb);
+            const int k6 = 2 * a + u, odd = k6 / 3, b3 = k6 - 3 * odd;       /* constants once unrolled */
+            f[u] = ipe_feature_split_sc(lm[b3], lv[b3], odd ? sc_odd : sc, odd ? sc2_odd : sc2, hb);
           }
+          unsigned whi, wlo;
           split_pair_f16(f[0], f[1], whi, wlo);
+          const int t = 3 * dp + a;                                          /* dword t of the lane's 12: wave-uniform */
+          char *dst = xq + (t >> 2) * BT * 16 + (t & 3) * 4;
+          *reinterpret_cast<unsigned *>(dst) = whi;
+          *reinterpret_cast<unsigned *>(dst + (BT / 2) * 16) = wlo;
         }
-        char *dst = xw + (6 * hb + 3 * qq + (t >> 2)) * BT * 16 + (t & 3) * 4;
-        *reinterpret_cast<unsigned *>(dst) = whi;
-        *reinterpret_cast<unsigned *>(dst + (BT / 2) * 16) = wlo;
+        sc *= 4.0f;
+        sc2 *= 16.0f;
       }
       }
       RN_STAMPW(A, 18);
@@ -946,7 +970,12 @@ __device__ __forceinline__ void level_fwd_split(const LevelArgs &A) {
       }
       SqAcc accs[2];
       sq_bias_now(p, accs[1]);
-      sq_layer<true>(p, ar, accs, false, R0, R0);
+      /* layer 0 writes R0 and reads the planes: R1 is idle through it and holds the planes' fragments; what held them is
+       * zeroed again as at the top of the run (R1 enters the trunk as it did) */
+      sq_load_ipe_frags(p, R1);
+      sq_layer<true>(p, ar, accs, false, R1, R0);
+#pragma unroll
+      for (int e = 0; e < 6; ++e) R1[e] = (v4uu){0, 0, 0, 0};
       RN_STAMPW(A, 4 + phase * 4);
 #pragma unroll 1
       for (int it = 0; it < 4; ++it) {
@@ -973,7 +1002,11 @@ __device__ __forceinline__ void level_fwd_split(const LevelArgs &A) {
     char *xs = Xb + col * 16;
     {
       SampleHeads sh;
-      load_heads(sh);
+      int g4; bool valid4;
+      load_heads(sh, g4, valid4);
+      /* the activations are evaluated HERE only: what the colour phase merely copies goes to the sample's record now (its
+       * rows and the pass's PX columns are unread until P6's history flush and the compositing of the ray) */
+      if (valid4 && h4 == 0) heads_store<NPS_EVAL, PSM>(sh, PS, PX, g4, RINGPS ? wave * 32 + (fresh_lane() & 31) : col);
       float ide[40];
 #pragma unroll
       for (int q = 36; q < 40; ++q) ide[q] = 0.0f;
@@ -1011,10 +1044,17 @@ __device__ __forceinline__ void level_fwd_split(const LevelArgs &A) {
     locate(g_w, rl_w, valid);
     int lane_w = lane6, pass_w = pass0;
     asm volatile("" : "+v"(lane_w), "+s"(pass_w));
-    if (valid && h6 == 0) {                                                           /* P6 */
-      SampleHeads sh;
-      load_heads(sh);
-      colour_store<false, NPS_EVAL, PSM, true, RINGPS>(A, sh, raw_rgb, PS, PX, n_tot, g_w, RINGPS ? wave * 32 + n6 : col);
+    if (valid) {                                                                      /* P6: both lanes of the sample */
+      int ci = RINGPS ? wave * 32 + n6 : col, pr = ps_row<PSM>(g_w) * NPS_EVAL;
+      asm volatile("" : "+v"(ci), "+v"(pr));           /* one address register each for the HD rows and the record */
+      float tint[3], raw_dif[3];
+#pragma unroll
+      for (int i = 0; i < 3; ++i) { tint[i] = PS[pr + PS_TINT + i]; raw_dif[i] = HD[(5 + i) * BT + ci]; }
+      /* (the half index laundered, the padding scale formed there: what P6 derives from either is otherwise hoisted to the
+       *  kernel's entry and parked in scratch across the trunks) */
+      int half = h6;
+      asm volatile("" : "+v"(half));
+      colour_store_halves<NPS_EVAL, PSM, true>(A, half, tint, raw_dif, raw_rgb, PS, g_w);
     }
     wave_sync();
     history_flush<NPS_EVAL, PSM>(A, PS, PX, n_tot, pass_w + wave * 32, wave * 32, (size_t)ray0 * N + pass_w + wave * 32, lane_w);

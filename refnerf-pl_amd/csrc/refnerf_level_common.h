@@ -384,6 +384,61 @@ __device__ __forceinline__ void colour_store(const LevelArgs &A, const SampleHea
   }
 }
 
+/* The split-f16 eval kernel's P4 / P6 (level_fwd_split) evaluate sample_heads ONCE per sample: P4 needs the activated heads
+ * on both half-waves for the directional encoding anyway, so it also parks what colour_store only copies (heads_store, one
+ * lane per sample), and P6 computes the colours alone, the sample's two lanes taking a column each (colour_store_halves). */
+template <int NP, int PSM>
+__device__ __forceinline__ void heads_store(const SampleHeads &s, float *PS, float *PX, int g_sample, int gcol) {
+  const int g = ps_row<PSM>(g_sample);
+  PS[g * NP + PS_DENSITY] = s.density;
+  PS[g * NP + PS_ROUGH] = s.rough;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    PS[g * NP + PS_NPRED + i] = s.npred[i];
+    PS[g * NP + PS_TINT + i] = s.tint[i];
+    PX[gcol * 3 + i] = s.gp[i];
+  }
+}
+/* colour_store<false, NP, PSM, true, PAD_HERE> without the copies, on BOTH lanes of a sample (lane n and lane 32 + n, `half`
+ * = 0 / 1, both active): half 1 computes the diffuse column, half 0 the specular one and -- with half 1's linear diffuse
+ * colour, fetched across the half-waves -- rgb.  One instruction stream for both halves: three sigmoids and six sRGB curves
+ * instead of six and nine.  Every stored value comes out of the same fp32 operations as in colour_store. */
+template <int NP, int PSM, bool PAD_HERE>
+__device__ __forceinline__ void colour_store_halves(const LevelArgs &A, int half, const float tint[3], const float raw_dif[3],
+                                                    const float raw_rgb[3], float *PS, int g_sample) {
+  const int g = ps_row<PSM>(g_sample);
+  const refnerf_level_cfg &cfg = A.cfg;
+  float own[3], rgb[3];        /* own: half 0 spec_lin, half 1 dif_lin */
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    const float sg = sigmoid_m<false>(half ? raw_dif[i] - LOG3_F : cfg.rgb_premultiplier * raw_rgb[i] + cfg.rgb_bias);
+    own[i] = half ? sg : tint[i] * sg;
+  }
+#pragma unroll
+  for (int i = 0; i < 3; ++i) rgb[i] = own[i] + __shfl_xor(own[i], 32, 64);      /* half 0: spec_lin + dif_lin */
+  if (cfg.srgb_mapping) {
+    if (cfg.srgb_mapping_normalization) {
+      float norm = fmaxf(fmaxf(fmaxf(rgb[0], rgb[1]), rgb[2]), 1.0f);
+#pragma unroll
+      for (int i = 0; i < 3; ++i) rgb[i] = m_div<false>(rgb[i], norm);
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      rgb[i] = clip01(linear_to_srgb<true>(rgb[i]));
+      own[i] = clip01(linear_to_srgb<true>(own[i]));
+    }
+  }
+  float pad = cfg.rgb_padding;
+  if (PAD_HERE) asm volatile("" : "+s"(pad));
+  const float pad_scale = (float)(1.0 + 2.0 * (double)pad);
+  const int own_slot = half ? PS_DIF : PS_SPC;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    PS[g * NP + own_slot + i] = own[i];
+    if (!half) PS[g * NP + PS_RGB + i] = rgb[i] * pad_scale - pad;
+  }
+}
+
 /* the per-sample history (84 B/sample, 48 MB per launch at C2) is written once and read by a later kernel:
  * non-temporal, so that it does not push the weight image out of the L2s it is streamed from */
 __device__ __forceinline__ void hist_store(float *p, float v) { __builtin_nontemporal_store(v, p); }
