@@ -491,6 +491,40 @@ typedef struct refnerf_noisy_rays_args {
 } refnerf_noisy_rays_args;
 int refnerf_noisy_rays(const refnerf_noisy_rays_args *args, void *stream);
 
+/* The two host-side stages of the proposal-network configuration (num_levels = 3, a separate PropMLP, dilation and
+ * interlevel loss on), one wave per ray, no host synchronisation, no allocation, every sum in one fixed order.
+ *
+ * refnerf_max_dilate_weights: stepfun.max_dilate_weights(t, w, dilation, domain = (lo, hi), renormalize = True) followed by
+ * [..., 1:-1] on both results (internal/models.py:167-187, internal/stepfun.py:92-131): what Model.__call__ puts in front
+ * of every level after the first.  p_i = w_i / max(eps^2, t_{i+1} - t_i), eps = FLT_EPSILON; knots x = the sorted union
+ * of t (M + 1 values), t[:-1] - dilation and t[1:] + dilation, clamped to [lo, hi] after sorting (bit-equal to torch.sort
+ * of the fp32 values); p'_j = max({ p_i : t_i - dilation <= x_j < t_{i+1} + dilation } U { 0 }) with the CLAMPED knot;
+ * w'_j = p'_j (x_{j+1} - x_j) / max(eps^2, sum_j w'_j), the sum over all 3 M intervals.  Written: knots 1 .. 3M - 1 and
+ * intervals 1 .. 3M - 2.  t must be nondecreasing along a ray; otherwise the values are meaningless (no access leaves
+ * the rows).  REFNERF_EINVAL: R < 0, M < 1, M > 171 (3 M - 2 > 512, the resampler's limit), a null pointer.  R == 0
+ * succeeds and launches nothing.
+ *
+ * refnerf_interlevel_forward / _backward: stepfun.lossfun_outer(t, w, t_env, w_env) of ONE proposal level (t_env, w_env:
+ * Np intervals) against the detached final level (t, w: N intervals) (internal/train_utils.py:151-162,
+ * internal/stepfun.py:31-89).  cy = [0, cumsum(w_env)] (accumulated in double); idx_lo(v) = the last k with
+ * t_env[k] <= v, or 0; idx_hi(v) = the first k with t_env[k] > v, or Np; w_outer_i = cy[idx_hi(t_{i+1})] - cy[idx_lo(t_i)];
+ * l_i = max(0, w_i - w_outer_i)^2 / (w_i + FLT_EPSILON).  Forward: d_ray_loss[r] = sum_i l_i; the caller sums the rays,
+ * divides by R N and applies Config.interlevel_loss_mult on the device.  Backward: d_upstream is a DEVICE scalar,
+ * d total / d (sum of d_ray_loss); d_g_w_env[r][k] = upstream * sum over the i with idx_lo(t_i) <= k < idx_hi(t_{i+1}) of
+ * -2 max(0, w_i - w_outer_i) / (w_i + FLT_EPSILON), an exact zero where no penalised interval covers k.  t, w and t_env
+ * get no gradient (the reference detaches the first two; the knots are not differentiable here).  Two calls on the same
+ * inputs are bit-identical.  REFNERF_EINVAL: R < 0, N or Np outside [1, 512], a null pointer.  R == 0 succeeds and
+ * launches nothing. */
+int refnerf_max_dilate_weights(const float *d_t /* [R][M+1] */, const float *d_w /* [R][M] */, int32_t R, int32_t M,
+                               float dilation, float domain_lo, float domain_hi, float *d_t_out /* [R][3M-1] */,
+                               float *d_w_out /* [R][3M-2] */, void *stream);
+int refnerf_interlevel_forward(const float *d_t /* [R][N+1] */, const float *d_w /* [R][N] */,
+                               const float *d_t_env /* [R][Np+1] */, const float *d_w_env /* [R][Np] */, int32_t R, int32_t N,
+                               int32_t Np, float *d_ray_loss /* [R] */, void *stream);
+int refnerf_interlevel_backward(const float *d_t, const float *d_w, const float *d_t_env, const float *d_w_env, int32_t R,
+                                int32_t N, int32_t Np, const float *d_upstream /* device scalar */,
+                                float *d_g_w_env /* [R][Np] */, void *stream);
+
 /* The optimiser step of the reference's loop, fused (nerf_system.py:205-217 configure_gradient_clipping +
  * on_after_backward, torch.optim.Adam.step): clip_grad_value_(grad_max_val), clip_grad_norm_(grad_max_norm) over ALL
  * tensors of the step, Adam (no AMSGrad, no weight decay), and the per-segment statistics grad_norm = |g|_2 and

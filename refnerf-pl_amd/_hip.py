@@ -163,6 +163,9 @@ def lib():
         L.refnerf_ray_regularisers_forward.argtypes = [C.POINTER(RegularisersArgs), _FP]
         L.refnerf_ray_regularisers_backward.argtypes = [C.POINTER(RegularisersArgs), _FP]
         L.refnerf_noisy_rays.argtypes = [C.POINTER(NoisyRaysArgs), _FP]
+        L.refnerf_max_dilate_weights.argtypes = [_FP, _FP, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, _FP, _FP, _FP]
+        L.refnerf_interlevel_forward.argtypes = [_FP] * 4 + [C.c_int32] * 3 + [_FP, _FP]
+        L.refnerf_interlevel_backward.argtypes = [_FP] * 4 + [C.c_int32] * 3 + [_FP, _FP, _FP]
         L.refnerf_optim_workspace_bytes.restype = C.c_size_t
         L.refnerf_optim_workspace_bytes.argtypes = [C.c_int64, C.c_int32]
         L.refnerf_optim_state_bytes.restype = C.c_size_t
@@ -624,6 +627,58 @@ def optim_adam_step(param, grad, exp_avg, exp_avg_sq, cfg: AdamCfg, state):
             raise ValueError("optim_adam_step: tensors differ in size")
     check(lib().refnerf_optim_adam_step(_ptr32(param), _ptr32(grad), _ptr32(exp_avg), _ptr32(exp_avg_sq), n, C.byref(cfg), ptr(state),
                                         stream_ptr()))
+
+
+def _rows32(t, shape, what):
+    """data pointer of a contiguous float32 device tensor of `shape` (None for an empty one: the library launches nothing then)"""
+    if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == tuple(shape)):
+        raise ValueError(f"{what} must be a contiguous float32 device tensor of shape {tuple(shape)}")
+    return C.c_void_p(t.data_ptr()) if t.numel() else None
+
+
+def max_dilate_weights(t, w, dilation, lo, hi):
+    """refnerf_max_dilate_weights: stepfun.max_dilate_weights(t, w, dilation, domain=(lo, hi), renormalize=True) and the
+    [..., 1:-1] of Model.__call__ in one launch.  t [R, M+1], w [R, M] (contiguous float32 device tensors, t nondecreasing)
+    -> (sdist [R, 3M-1], weights [R, 3M-2])."""
+    require_device()
+    if t.dim() != 2 or w.dim() != 2:
+        raise ValueError("max_dilate_weights: t [R, M+1] and w [R, M]")
+    R, M = w.shape
+    sd = torch.empty((R, max(3 * M - 1, 0)), dtype=torch.float32, device=t.device)
+    wd = torch.empty((R, max(3 * M - 2, 0)), dtype=torch.float32, device=t.device)
+    check(lib().refnerf_max_dilate_weights(_rows32(t, (R, M + 1), "max_dilate_weights: t"), _rows32(w, (R, M), "max_dilate_weights: w"),
+                                           R, M, float(dilation), float(lo), float(hi), ptr(sd) if sd.numel() else None,
+                                           ptr(wd) if wd.numel() else None, stream_ptr()))
+    return sd, wd
+
+
+def _interlevel_args(t, w, t_env, w_env):
+    if w.dim() != 2 or w_env.dim() != 2 or w.shape[0] != w_env.shape[0]:
+        raise ValueError("interlevel loss: w [R, N] and w_env [R, Np]")
+    (R, N), Np = w.shape, w_env.shape[1]
+    return (_rows32(t, (R, N + 1), "interlevel loss: t"), _rows32(w, (R, N), "interlevel loss: w"),
+            _rows32(t_env, (R, Np + 1), "interlevel loss: t_env"), _rows32(w_env, (R, Np), "interlevel loss: w_env"), R, N, Np)
+
+
+def interlevel_forward(t, w, t_env, w_env):
+    """refnerf_interlevel_forward: per-ray sums [R] of stepfun.lossfun_outer(t, w, t_env, w_env) (t [R, N+1], w [R, N]: the
+    final level; t_env [R, Np+1], w_env [R, Np]: one proposal level; contiguous float32 device tensors)."""
+    require_device()
+    args = _interlevel_args(t, w, t_env, w_env)
+    ray_loss = torch.empty((args[4],), dtype=torch.float32, device=w.device)
+    check(lib().refnerf_interlevel_forward(*args, ptr(ray_loss) if ray_loss.numel() else None, stream_ptr()))
+    return ray_loss
+
+
+def interlevel_backward(t, w, t_env, w_env, upstream):
+    """refnerf_interlevel_backward -> g_w_env [R, Np]; upstream: a one-element float32 device tensor, the gradient of the
+    total w.r.t. the sum of interlevel_forward's per-ray sums."""
+    require_device()
+    args = _interlevel_args(t, w, t_env, w_env)
+    g = torch.empty((args[4], args[6]), dtype=torch.float32, device=w.device)
+    check(lib().refnerf_interlevel_backward(*args, _rows32(upstream.reshape(1), (1,), "interlevel loss: upstream"),
+                                            ptr(g) if g.numel() else None, stream_ptr()))
+    return g
 
 
 def sample_intervals(t, logits, n, smin=0.0, smax=1.0):

@@ -32,6 +32,7 @@
 #include "refnerf_rays.h"
 #include "refnerf_optim.h"
 #include "refnerf_regularisers.h"
+#include "refnerf_proposal.h"
 #include "refnerf_pack_common.h"
 #include "refnerf_sq_host.h"
 #include "refnerf_sq_layout.h"
@@ -1291,6 +1292,53 @@ int refnerf_noisy_rays(const refnerf_noisy_rays_args *args, void *stream) {
   const size_t total = (size_t)args->n * args->a;
   if (total > (size_t)INT32_MAX) return fail(REFNERF_EINVAL, "refnerf_noisy_rays: n * a must be below 2^31%s");
   hipLaunchKernelGGL(rn::noisy_rays_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *args);
+  HIP_TRY(hipGetLastError());
+  return REFNERF_OK;
+}
+
+/* ---- dilation between proposal levels and the interlevel loss (refnerf_proposal.h) ---- */
+int refnerf_max_dilate_weights(const float *d_t, const float *d_w, int32_t R, int32_t M, float dilation, float domain_lo,
+                               float domain_hi, float *d_t_out, float *d_w_out, void *stream) {
+  if (R < 0) return fail(REFNERF_EINVAL, "refnerf_max_dilate_weights: R must not be negative%s");
+  if (M < 1 || M > rn::DILATE_MAX_M)
+    return fail(REFNERF_EINVAL, "refnerf_max_dilate_weights: M must be in [1,171] (the dilated step function has 3 M - 2 intervals; the resampler takes at most 512)%s");
+  if (R == 0) return REFNERF_OK;                           /* nothing to do: the pointers are not looked at */
+  if (!d_t || !d_w || !d_t_out || !d_w_out) return fail(REFNERF_EINVAL, "refnerf_max_dilate_weights: null pointer%s");
+  hipLaunchKernelGGL(rn::max_dilate_weights_kernel, dim3((R + rn::PROP_WAVES - 1) / rn::PROP_WAVES), dim3(64 * rn::PROP_WAVES), 0,
+                     (hipStream_t)stream, d_t, d_w, R, M, dilation, domain_lo, domain_hi, d_t_out, d_w_out);
+  HIP_TRY(hipGetLastError());
+  return REFNERF_OK;
+}
+
+namespace {
+static int check_interlevel(const char *fn, int32_t R, int32_t N, int32_t Np) {
+  if (R < 0) return fail(REFNERF_EINVAL, "%s: R must not be negative", fn);
+  if (N < 1 || N > rn::INTERLEVEL_MAX_N || Np < 1 || Np > rn::INTERLEVEL_MAX_N)
+    return fail(REFNERF_EINVAL, "%s: N and Np must be in [1,512]", fn);
+  return REFNERF_OK;
+}
+}  // namespace
+
+int refnerf_interlevel_forward(const float *d_t, const float *d_w, const float *d_t_env, const float *d_w_env, int32_t R,
+                               int32_t N, int32_t Np, float *d_ray_loss, void *stream) {
+  const char *fn = "refnerf_interlevel_forward";
+  if (int rc = check_interlevel(fn, R, N, Np)) return rc;
+  if (R == 0) return REFNERF_OK;
+  if (!d_t || !d_w || !d_t_env || !d_w_env || !d_ray_loss) return fail(REFNERF_EINVAL, "%s: null pointer", fn);
+  hipLaunchKernelGGL(rn::interlevel_fwd_kernel, dim3((R + rn::PROP_WAVES - 1) / rn::PROP_WAVES), dim3(64 * rn::PROP_WAVES), 0,
+                     (hipStream_t)stream, d_t, d_w, d_t_env, d_w_env, R, N, Np, d_ray_loss);
+  HIP_TRY(hipGetLastError());
+  return REFNERF_OK;
+}
+
+int refnerf_interlevel_backward(const float *d_t, const float *d_w, const float *d_t_env, const float *d_w_env, int32_t R,
+                                int32_t N, int32_t Np, const float *d_upstream, float *d_g_w_env, void *stream) {
+  const char *fn = "refnerf_interlevel_backward";
+  if (int rc = check_interlevel(fn, R, N, Np)) return rc;
+  if (R == 0) return REFNERF_OK;
+  if (!d_t || !d_w || !d_t_env || !d_w_env || !d_upstream || !d_g_w_env) return fail(REFNERF_EINVAL, "%s: null pointer", fn);
+  hipLaunchKernelGGL(rn::interlevel_bwd_kernel, dim3((R + rn::PROP_WAVES - 1) / rn::PROP_WAVES), dim3(64 * rn::PROP_WAVES), 0,
+                     (hipStream_t)stream, d_t, d_w, d_t_env, d_w_env, R, N, Np, d_upstream, d_g_w_env);
   HIP_TRY(hipGetLastError());
   return REFNERF_OK;
 }

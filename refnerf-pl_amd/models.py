@@ -745,19 +745,25 @@ class Model(nn.Module):
             if num_samples <= 1:
                 raise ValueError(f'num_samples must be > 1, is {num_samples}.')   # stepfun.py:234-235
             # models.py:167-186: after the first level optionally dilate the step function the next level
-            # resamples from (a few torch ops on the detached [R, M] step function; the kernel then resamples
-            # from 3M-2 intervals)
+            # resamples from (torch ops on the detached [R, M] step function, or one kernel under Config.hip_fused_proposal;
+            # the level kernel then resamples from 3M-2 intervals)
             dilation = self.dilation_bias + self.dilation_multiplier * (self.init_s_far - self.init_s_near) / prod_num_samples
             prod_num_samples *= num_samples
             if i_level > 0 and (self.dilation_bias > 0 or self.dilation_multiplier > 0):
                 from . import stepfun
-                with torch.no_grad():
-                    sdist, weights = stepfun.max_dilate_weights(sdist.detach(), weights.detach(), dilation,
-                                                                domain=(self.init_s_near, self.init_s_far), renormalize=True)
-                    sdist, weights = sdist[..., 1:-1].contiguous(), weights[..., 1:-1].contiguous()
-                if weights.shape[-1] > 512:
-                    raise ValueError(f'dilated step function has {weights.shape[-1]} intervals; the fused resampler '
+                n_dilated = 3 * weights.shape[-1] - 2        # what comes out of the dilation and its [..., 1:-1]
+                if n_dilated > 512:
+                    raise ValueError(f'dilated step function has {n_dilated} intervals; the fused resampler '
                                      'takes at most 512 (num_samples <= 171 per level with dilation)')
+                with torch.no_grad():
+                    if getattr(self.config, "hip_fused_proposal", False) and sdist.is_cuda:
+                        # the sort, the comparison masks, the pdf / weight conversions and the renormalisation in ONE launch
+                        sdist, weights = _hip.max_dilate_weights(sdist.detach().contiguous(), weights.detach().contiguous(), dilation,
+                                                                 self.init_s_near, self.init_s_far)
+                    else:
+                        sdist, weights = stepfun.max_dilate_weights(sdist.detach(), weights.detach(), dilation,
+                                                                    domain=(self.init_s_near, self.init_s_far), renormalize=True)
+                        sdist, weights = sdist[..., 1:-1].contiguous(), weights[..., 1:-1].contiguous()
             mlp = self.prop_mlp if is_prop else self.nerf_mlp
             cfg = self._level_cfg(mlp, num_samples, weights.shape[-1], train_frac, compute_extras)
             sd_in, w_in = sdist, weights                     # this level's incoming step function (the specular-density launch re-reads it)

@@ -216,6 +216,47 @@ def interlevel_loss(ray_history, config):
     return config.interlevel_loss_mult * total
 
 
+class _FusedInterlevel(torch.autograd.Function):
+    """sum over rays and intervals of stepfun.lossfun_outer(t, w, t_env, w_env) for ONE proposal level as a single autograd
+    node on refnerf_interlevel_forward / _backward (Config.hip_fused_proposal): what the cumsum, the two searchsorted calls,
+    the two gathers and their autograd compute, in one launch each way.  Only w_env gets a gradient: the final level's
+    (t, w) are detached by the loss, and the knots t_env are not differentiable."""
+
+    @staticmethod
+    def forward(ctx, t, w, t_env, w_env):
+        from . import _hip
+        rows = tuple(x.detach().to(torch.float32).reshape(-1, x.shape[-1]).contiguous() for x in (t, w, t_env, w_env))
+        ctx.rows, ctx.shape = rows, w_env.shape
+        return _hip.interlevel_forward(*rows).sum()
+
+    @staticmethod
+    def backward(ctx, g_sum):
+        from . import _hip
+        # the upstream gradient stays on the device (no host synchronisation)
+        g = _hip.interlevel_backward(*ctx.rows, g_sum.detach().to(torch.float32).reshape(1).contiguous())
+        return None, None, None, g.reshape(ctx.shape)
+
+
+_INTERLEVEL_MAX_INTERVALS = 512     # refnerf_interlevel_forward / _backward: N and Np in [1, 512]
+
+
+def fused_interlevel_supported(ray_history):
+    """The kernels take CUDA tensors of 1..512 intervals per level."""
+    return all(h['weights'].is_cuda and h['sdist'].is_cuda and 1 <= h['weights'].shape[-1] <= _INTERLEVEL_MAX_INTERVALS and
+               h['sdist'].shape[-1] == h['weights'].shape[-1] + 1 for h in ray_history)
+
+
+def fused_interlevel_loss(ray_history, config):
+    """interlevel_loss through the fused kernels, one autograd node per proposal level: the same value (fp32 summation
+    order aside; the kernel accumulates in double) and the same gradient into the proposal levels' weights."""
+    c = ray_history[-1]['sdist'].detach()
+    w = ray_history[-1]['weights'].detach()
+    total = 0.
+    for ray_results in ray_history[:-1]:
+        total = total + _FusedInterlevel.apply(c, w, ray_results['sdist'].detach(), ray_results['weights']) / float(w.numel())
+    return config.interlevel_loss_mult * total
+
+
 _REG_TERMS = ('weights_entropy', 'acc', 'diffuse_consistency', 'specular_consistency', 'normals_consistency',
               'distance_consistency')        # the order of the kernels' scales / of the node's per-term output
 _REG_INPUTS = ('weights', 'acc', 'distance', 'diffuse', 'specular', 'normals')
@@ -286,7 +327,8 @@ def fused_ray_regularisers(model, rays, noisy_rays, renderings, renderings_noise
     'diffuse_consistency', 'specular_consistency', 'normals_consistency', 'acc', 'distance_consistency' and
     'weights_entropy' that Config switches on, with the same values (fp32 summation order aside) and the same gradients into
     the clean and the noisy renderings and ray_history['weights'].  Flat batches ([R, .] rays) on the device; nothing is
-    read back to the host.  Depth smoothness (patch batches) and the interlevel loss stay ATen."""
+    read back to the host.  Depth smoothness (patch batches) stays ATen; the interlevel loss has its own kernels
+    (fused_interlevel_loss, Config.hip_fused_proposal)."""
     from . import _hip
     dev = renderings[0]['acc'].device
     f32 = dict(dtype=torch.float32, device=dev)
@@ -508,8 +550,8 @@ def compute_losses(model, batch, rays, renderings, ray_history, config, renderin
                    warmup_ratio=1.):
     """The loss assembly of NeRFSystem.training_step (nerf_system.py:118-180) on already computed
     renderings: returns (total, dict of terms, stats).  Config.hip_fused_losses / hip_fused_regularisers route the three Ref-NeRF
-    terms / the six geometry regularisers through their fused kernels (same keys, same order); depth smoothness and the
-    interlevel loss stay ATen."""
+    terms / the six geometry regularisers through their fused kernels and Config.hip_fused_proposal the interlevel loss through
+    its own (same keys, same order); depth smoothness stays ATen."""
     losses = {}
     fused = getattr(config, 'hip_fused_losses', False) and fused_losses_supported(config) and renderings[0]['rgb'].is_cuda
     if fused:      # opt-in: the three Ref-NeRF terms of every level through refnerf_losses_forward / _backward
@@ -518,7 +560,9 @@ def compute_losses(model, batch, rays, renderings, ray_history, config, renderin
         data_loss, stats = compute_data_loss(batch, renderings, rays, config)
     losses['data'] = data_loss
     if config.interlevel_loss_mult > 0:
-        losses['interlevel'] = interlevel_loss(ray_history, config)
+        # opt-in: one launch each way per proposal level (refnerf_interlevel_forward / _backward)
+        fused_prop = getattr(config, 'hip_fused_proposal', False) and fused_interlevel_supported(ray_history)
+        losses['interlevel'] = fused_interlevel_loss(ray_history, config) if fused_prop else interlevel_loss(ray_history, config)
     if _any_positive(config, 'orientation_coarse_loss_mult', 'orientation_loss_mult'):
         losses['orientation'] = o_loss if fused else orientation_loss(rays, model, ray_history, config)
     if _any_positive(config, 'predicted_normal_coarse_loss_mult', 'predicted_normal_loss_mult'):
