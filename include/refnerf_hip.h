@@ -565,12 +565,56 @@ int refnerf_optim_finalize(void *d_state, size_t state_bytes, int32_t n_tensors,
 int refnerf_optim_adam_step(float *d_param, float *d_grad, float *d_exp_avg, float *d_exp_avg_sq, int64_t n,
                             const refnerf_adam_cfg *cfg, const void *d_state, void *stream);
 
+/* Test-image evaluation, the metric half of the reference's test_step (nerf_system.py:391-444), on the device.
+ * Images are double [H][W][C] with a row pitch in ELEMENTS (>= W * C; a border crop is a pointer offset), 8-byte aligned;
+ * all arithmetic is float64, as in the reference, which casts to float64 before it evaluates.  Every sum over pixels is a
+ * two-stage reduction in one fixed order (per-workgroup partials in d_workspace, then one workgroup adds them in index
+ * order): no float atomics, two runs are bit-identical, and a pitched view gives the bits of its contiguous copy.  No
+ * entry synchronises the host or allocates; results are written to device memory at d_out.  d_workspace holds at least
+ * refnerf_image_workspace_bytes(H, W, C) bytes (0 for bad sizes; enough for every entry at that shape, for
+ * refnerf_weighted_mae with n = H * W) and must not be shared by calls on different streams.
+ *
+ *   refnerf_image_mse      d_out[0] = mean over H W C of (q(a) - b)^2, d_out[1] = its PSNR, mse_to_psnr as the reference
+ *                          evaluates it: float32(-10 / float32(ln 10)) * ln(mse).  q(x) = rint(x * 255) / 255 (half to
+ *                          even, torch.round) when quantize_a is set, else x.  C = 1 gives the disparity MSE.
+ *   refnerf_image_ssim     d_out[0] = dm_pix.ssim(a, b) with its defaults (max_val 1, 11 taps, sigma 1.5, k1 0.01, k2 0.03):
+ *                          taps g[i] = exp(-0.5 ((i - 5) / 1.5)^2) normalised to sum 1 (host, double); F = 'valid'
+ *                          separable correlation along H then W per channel; mu = F(.), s_aa = max(e, F(a^2) - mu_a^2),
+ *                          s_bb alike, e = (2^-23)^2, s = F(ab) - mu_a mu_b, s_ab = sign(s) min(sqrt(s_aa s_bb), |s|);
+ *                          map = (2 mu_a mu_b + c1)(2 s_ab + c2) / ((mu_a^2 + mu_b^2 + c1)(s_aa + s_bb + c2)), c1 = 1e-4,
+ *                          c2 = 9e-4; the mean over the [H-10][W-10][C] map.  d_map (optional, dense) receives the map.
+ *                          quantize_a as above.  H < 11 or W < 11: REFNERF_EINVAL (the reference's map would be empty).
+ *   refnerf_color_correct  image.color_correct(img, ref, num_iters, eps) (internal/image.py:84-127), C = 3: per iteration the
+ *                          masked normal equations of the ten-term quadratic expansion, one 10 x 10 pseudo-inverse solve
+ *                          per channel (eigenvalues <= 10 * 2^-52 * lambda_max dropped; an all-masked channel gives a
+ *                          zero warp, as lstsq does), x <- clip(a W, 0, 1).  d_out: the corrected image, dense [H][W][3],
+ *                          must not overlap d_img; d_warp (optional): the last [10][3] warp.  num_iters = 0 copies the
+ *                          input.  3 launches per iteration.  Agrees with the reference's lstsq to 1e-13 where the masked
+ *                          systems are well conditioned; near-rank-deficient images (a constant colour) are outside
+ *                          that: the rank decision on A^T A is not lstsq's on A.
+ *   refnerf_weighted_mae   ref_utils.compute_weighted_mae: d_out[0] = sum w acos(clip(n . n_gt, +-(1 - 2^-23))) / sum w
+ *                          * 180 / pi; d_weights [n], d_normals and d_normals_gt [n][3], dense.
+ * REFNERF_EINVAL: a null pointer (d_map / d_warp may be null), C outside 1..4 (colour correction: C != 3), a pitch below
+ * W * C, num_iters outside 0..64, a non-finite eps, a misaligned pointer, a workspace too small, H W C >= 2^31. */
+size_t refnerf_image_workspace_bytes(int32_t H, int32_t W, int32_t C);
+int refnerf_image_mse(const double *d_a, int64_t pitch_a, const double *d_b, int64_t pitch_b, int32_t H, int32_t W, int32_t C,
+                      int32_t quantize_a, double *d_out /* [2] */, void *d_workspace, size_t workspace_bytes, void *stream);
+int refnerf_image_ssim(const double *d_a, int64_t pitch_a, const double *d_b, int64_t pitch_b, int32_t H, int32_t W, int32_t C,
+                       int32_t quantize_a, double *d_out /* [1] */, double *d_map /* [H-10][W-10][C] or NULL */,
+                       void *d_workspace, size_t workspace_bytes, void *stream);
+int refnerf_color_correct(const double *d_img, int64_t pitch_img, const double *d_ref, int64_t pitch_ref, int32_t H, int32_t W,
+                          int32_t C, int32_t num_iters, double eps, double *d_out /* [H][W][3] */,
+                          double *d_warp /* [10][3] or NULL */, void *d_workspace, size_t workspace_bytes, void *stream);
+int refnerf_weighted_mae(const double *d_weights, const double *d_normals, const double *d_normals_gt, int64_t n,
+                         double *d_out /* [1] */, void *d_workspace, size_t workspace_bytes, void *stream);
+
 /* Total duration (ms) and count of the `refnerf_level_forward` kernels launched
  * since refnerf_set_timing(1), from HIP event pairs on the launch stream.
  * Used by bench.py for the roofline line. */
 enum { REFNERF_TIMER_FORWARD = 0,   /* the level kernel of refnerf_level_forward / _forward_train           */
        REFNERF_TIMER_BACKWARD = 1,  /* the per-sample backward kernel of refnerf_level_backward              */
-       REFNERF_TIMER_WGRAD = 2 };   /* its weight-gradient GEMM                                              */
+       REFNERF_TIMER_WGRAD = 2,     /* its weight-gradient GEMM                                              */
+       REFNERF_TIMER_IMAGE = 3 };   /* one pair per image-evaluation entry, around all of its launches       */
 int refnerf_set_timing(int enable);
 int refnerf_get_timing(double *total_ms, int64_t *launches);                         /* REFNERF_TIMER_FORWARD */
 int refnerf_get_timing_family(int family, double *total_ms, int64_t *launches);

@@ -175,6 +175,13 @@ def lib():
                                           _FP, C.c_size_t, C.c_int32, _FP]
         L.refnerf_optim_finalize.argtypes = [_FP, C.c_size_t, C.c_int32, C.c_double, _FP]
         L.refnerf_optim_adam_step.argtypes = [_FP, _FP, _FP, _FP, C.c_int64, C.POINTER(AdamCfg), _FP, _FP]
+        L.refnerf_image_workspace_bytes.restype = C.c_size_t
+        L.refnerf_image_workspace_bytes.argtypes = [C.c_int32] * 3
+        L.refnerf_image_mse.argtypes = [_FP, C.c_int64, _FP, C.c_int64] + [C.c_int32] * 4 + [_FP, _FP, C.c_size_t, _FP]
+        L.refnerf_image_ssim.argtypes = [_FP, C.c_int64, _FP, C.c_int64] + [C.c_int32] * 4 + [_FP, _FP, _FP, C.c_size_t, _FP]
+        L.refnerf_color_correct.argtypes = [_FP, C.c_int64, _FP, C.c_int64] + [C.c_int32] * 4 + [C.c_double, _FP, _FP, _FP,
+                                                                                                  C.c_size_t, _FP]
+        L.refnerf_weighted_mae.argtypes = [_FP, _FP, _FP, C.c_int64, _FP, _FP, C.c_size_t, _FP]
         L.refnerf_get_timing.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_int64)]
         L.refnerf_get_timing_family.argtypes = [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
         if L.refnerf_abi_version() != ABI_VERSION:
@@ -708,11 +715,81 @@ def integrated_dir_enc(xyz, kappa_inv):
     return out
 
 
+def _image64(t, what):
+    """(pointer, row pitch in elements) of a float64 device image [H, W, C]; a view whose pixels are dense and whose rows are
+    a fixed distance apart (a border crop) is passed as it is, anything else is made contiguous first."""
+    if not (t.is_cuda and t.dtype == torch.float64 and t.dim() == 3):
+        raise ValueError(f"{what}: a float64 device image [H, W, C] is required")
+    H, W, Cn = t.shape
+    if not (t.stride(2) == 1 and t.stride(1) == Cn and (H == 1 or t.stride(0) >= W * Cn)):
+        t = t.contiguous()
+    return t, C.c_void_p(t.data_ptr()), int(t.stride(0)) if H > 1 else W * Cn
+
+
+def image_workspace(H: int, W: int, Cn: int, device) -> torch.Tensor:
+    """The workspace of the image entries at one shape (refnerf_image_workspace_bytes)."""
+    nbytes = int(lib().refnerf_image_workspace_bytes(int(H), int(W), int(Cn)))
+    if nbytes == 0:
+        raise ValueError(f"image_workspace: [{H}, {W}, {Cn}] is not a valid image shape (C in 1..4, H * W * C < 2^31)")
+    return torch.empty(nbytes // 8, dtype=torch.float64, device=device)
+
+
+def _image_pair(a, b, what):
+    if a.shape != b.shape:
+        raise ValueError(f"{what}: the images differ in shape: {tuple(a.shape)} and {tuple(b.shape)}")
+    a, pa, sa = _image64(a, what)
+    b, pb, sb = _image64(b, what)
+    return (a, b), (pa, sa, pb, sb) + tuple(int(s) for s in a.shape)
+
+
+def image_mse(a, b, quantize_a=False, workspace=None):
+    """refnerf_image_mse: a float64 device tensor [2] = (mean (q(a) - b)^2, its PSNR)."""
+    keep, args = _image_pair(a, b, "image_mse")
+    ws = image_workspace(*a.shape, a.device) if workspace is None else workspace
+    out = torch.empty(2, dtype=torch.float64, device=a.device)
+    check(lib().refnerf_image_mse(*args, int(bool(quantize_a)), ptr(out), ptr(ws), ws.numel() * 8, stream_ptr()))
+    return out
+
+
+def image_ssim(a, b, quantize_a=False, return_map=False, workspace=None):
+    """refnerf_image_ssim: the mean SSIM as a float64 device scalar (and the [H-10, W-10, C] map when asked for)."""
+    keep, args = _image_pair(a, b, "image_ssim")
+    H, W, Cn = a.shape
+    ws = image_workspace(H, W, Cn, a.device) if workspace is None else workspace
+    out = torch.empty(1, dtype=torch.float64, device=a.device)
+    smap = torch.empty((max(H - 10, 0), max(W - 10, 0), Cn), dtype=torch.float64, device=a.device) if return_map else None
+    check(lib().refnerf_image_ssim(*args, int(bool(quantize_a)), ptr(out), ptr(smap), ptr(ws), ws.numel() * 8, stream_ptr()))
+    return (out[0], smap) if return_map else out[0]
+
+
+def color_correct(img, ref, num_iters=5, eps=0.5 / 255, return_warp=False, workspace=None):
+    """refnerf_color_correct: the corrected image, dense float64 [H, W, 3] (and the last [10, 3] warp when asked for)."""
+    keep, args = _image_pair(img, ref, "color_correct")
+    ws = image_workspace(*img.shape, img.device) if workspace is None else workspace
+    out = torch.empty(tuple(img.shape), dtype=torch.float64, device=img.device)
+    warp = torch.zeros((10, 3), dtype=torch.float64, device=img.device) if return_warp else None
+    check(lib().refnerf_color_correct(*args, int(num_iters), float(eps), ptr(out), ptr(warp), ptr(ws), ws.numel() * 8, stream_ptr()))
+    return (out, warp) if return_warp else out
+
+
+def weighted_mae(weights, normals, normals_gt, workspace=None):
+    """refnerf_weighted_mae: the weighted mean angular error in degrees as a float64 device scalar."""
+    n = weights.numel()
+    for t, m, what in ((weights, n, "weights"), (normals, 3 * n, "normals"), (normals_gt, 3 * n, "normals_gt")):
+        if not (t.is_cuda and t.dtype == torch.float64 and t.numel() == m):
+            raise ValueError(f"weighted_mae: {what} must be a float64 device tensor of {m} elements")
+    w, a, b = weights.contiguous(), normals.contiguous(), normals_gt.contiguous()
+    ws = image_workspace(1, max(n, 1), 1, w.device) if workspace is None else workspace
+    out = torch.empty(1, dtype=torch.float64, device=w.device)
+    check(lib().refnerf_weighted_mae(ptr(w), ptr(a), ptr(b), n, ptr(out), ptr(ws), ws.numel() * 8, stream_ptr()))
+    return out[0]
+
+
 def set_timing(enable: bool):
     lib().refnerf_set_timing(int(enable))
 
 
-TIMER_FORWARD, TIMER_BACKWARD, TIMER_WGRAD = 0, 1, 2
+TIMER_FORWARD, TIMER_BACKWARD, TIMER_WGRAD, TIMER_IMAGE = 0, 1, 2, 3
 
 
 def get_timing(family: int = TIMER_FORWARD):

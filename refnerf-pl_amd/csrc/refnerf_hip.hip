@@ -33,6 +33,7 @@
 #include "refnerf_optim.h"
 #include "refnerf_regularisers.h"
 #include "refnerf_proposal.h"
+#include "refnerf_image.h"
 #include "refnerf_pack_common.h"
 #include "refnerf_sq_host.h"
 #include "refnerf_sq_layout.h"
@@ -1454,6 +1455,148 @@ int refnerf_optim_adam_step(float *d_param, float *d_grad, float *d_exp_avg, flo
   hipLaunchKernelGGL(rn::optim_adam_kernel, dim3((unsigned)blocks), dim3(rn::OPTIM_THREADS), 0, (hipStream_t)stream, a);
   HIP_TRY(hipGetLastError());
   return REFNERF_OK;
+}
+
+/* ---- test-image evaluation (refnerf_image.h) ---- */
+namespace {
+struct ImageLayout { size_t sq_blocks, px_blocks, ssim_tiles, scratch /* doubles shared by the reductions */, total /* bytes */; };
+bool image_layout(int32_t H, int32_t W, int32_t C, ImageLayout *L) {
+  if (H <= 0 || W <= 0 || C < 1 || C > 4 || (int64_t)H * W * C > INT32_MAX) return false;
+  const int64_t npix = (int64_t)H * W;
+  L->sq_blocks = (size_t)((npix * C + rn::IMG_ELEMS_PER_BLOCK - 1) / rn::IMG_ELEMS_PER_BLOCK);
+  L->px_blocks = (size_t)((npix + rn::IMG_PIX_PER_BLOCK - 1) / rn::IMG_PIX_PER_BLOCK);
+  L->ssim_tiles = 0;
+  if (H >= rn::SSIM_TAPS && W >= rn::SSIM_TAPS)
+    L->ssim_tiles = (size_t)((H - rn::SSIM_TAPS + rn::SSIM_TILE) / rn::SSIM_TILE) * (size_t)((W - rn::SSIM_TAPS + rn::SSIM_TILE) / rn::SSIM_TILE);
+  L->scratch = L->sq_blocks;
+  if (2 * L->px_blocks > L->scratch) L->scratch = 2 * L->px_blocks;
+  if (L->ssim_tiles > L->scratch) L->scratch = L->ssim_tiles;
+  /* colour correction: the warp [10][3] (32 doubles), then [px_blocks][3][65] partials */
+  L->total = (L->scratch + 32 + L->px_blocks * 3 * rn::CC_PART) * sizeof(double);
+  return true;
+}
+int check_image_pair(const char *fn, const void *a, int64_t pitch_a, const void *b, int64_t pitch_b, int32_t H, int32_t W, int32_t C,
+                     const void *d_out, const void *ws, ImageLayout *L) {
+  if (!a || !b || !d_out || !ws) return fail(REFNERF_EINVAL, "%s: null pointer", fn);
+  if (C < 1 || C > 4) return fail(REFNERF_EINVAL, "%s: C must be in [1,4]", fn);
+  if (!image_layout(H, W, C, L)) return fail(REFNERF_EINVAL, "%s: H and W must be positive and H * W * C below 2^31", fn);
+  if (pitch_a < (int64_t)W * C || pitch_b < (int64_t)W * C) return fail(REFNERF_EINVAL, "%s: a row pitch below W * C", fn);
+  if (((uintptr_t)a | (uintptr_t)b | (uintptr_t)d_out | (uintptr_t)ws) & 7u) return fail(REFNERF_EINVAL, "%s: misaligned pointer", fn);
+  return REFNERF_OK;
+}
+int image_finalize(hipStream_t st, const double *partials, size_t n_part, int n_val, int mode, double denom, double *d_out) {
+  hipLaunchKernelGGL(rn::image_finalize_kernel, dim3(1), dim3(rn::IMG_THREADS), 0, st, partials, (int32_t)n_part, n_val, mode, denom, d_out);
+  HIP_TRY(hipGetLastError());
+  return REFNERF_OK;
+}
+}  // namespace
+
+size_t refnerf_image_workspace_bytes(int32_t H, int32_t W, int32_t C) {
+  ImageLayout L;
+  return image_layout(H, W, C, &L) ? L.total : 0;
+}
+
+int refnerf_image_mse(const double *d_a, int64_t pitch_a, const double *d_b, int64_t pitch_b, int32_t H, int32_t W, int32_t C,
+                      int32_t quantize_a, double *d_out, void *d_workspace, size_t workspace_bytes, void *stream) {
+  const char *fn = "refnerf_image_mse";
+  ImageLayout L;
+  if (int rc = check_image_pair(fn, d_a, pitch_a, d_b, pitch_b, H, W, C, d_out, d_workspace, &L)) return rc;
+  if (workspace_bytes < L.sq_blocks * sizeof(double)) return fail(REFNERF_EINVAL, "%s: workspace too small (see refnerf_image_workspace_bytes)", fn);
+  hipStream_t st = (hipStream_t)stream;
+  double *partials = static_cast<double *>(d_workspace);
+  const int64_t n = (int64_t)H * W * C;
+  long tslot;
+  { int trc = timer_begin(st, &tslot, REFNERF_TIMER_IMAGE); if (trc) return trc; }
+  hipLaunchKernelGGL(rn::image_sqerr_kernel, dim3((unsigned)L.sq_blocks), dim3(rn::IMG_THREADS), 0, st, d_a, pitch_a, d_b, pitch_b,
+                     W * C, n, quantize_a ? 1 : 0, partials);
+  HIP_TRY(hipGetLastError());
+  if (int rc = image_finalize(st, partials, L.sq_blocks, 1, rn::IMG_FIN_MSE_PSNR, (double)n, d_out)) return rc;
+  return timer_end(st, tslot);
+}
+
+int refnerf_image_ssim(const double *d_a, int64_t pitch_a, const double *d_b, int64_t pitch_b, int32_t H, int32_t W, int32_t C,
+                       int32_t quantize_a, double *d_out, double *d_map, void *d_workspace, size_t workspace_bytes, void *stream) {
+  const char *fn = "refnerf_image_ssim";
+  ImageLayout L;
+  if (int rc = check_image_pair(fn, d_a, pitch_a, d_b, pitch_b, H, W, C, d_out, d_workspace, &L)) return rc;
+  if (H < rn::SSIM_TAPS || W < rn::SSIM_TAPS) return fail(REFNERF_EINVAL, "%s: H and W must be at least 11 (the filter's support)", fn);
+  if ((uintptr_t)d_map & 7u) return fail(REFNERF_EINVAL, "%s: misaligned pointer", fn);
+  if (workspace_bytes < L.ssim_tiles * sizeof(double)) return fail(REFNERF_EINVAL, "%s: workspace too small (see refnerf_image_workspace_bytes)", fn);
+  rn::SsimTaps taps;
+  double sum = 0.0;
+  for (int i = 0; i < rn::SSIM_TAPS; ++i) {
+    const double z = (i - 5) / 1.5;
+    taps.g[i] = std::exp(-0.5 * (z * z));
+    sum += taps.g[i];
+  }
+  for (int i = 0; i < rn::SSIM_TAPS; ++i) taps.g[i] /= sum;
+  hipStream_t st = (hipStream_t)stream;
+  double *partials = static_cast<double *>(d_workspace);
+  const int OH = H - (rn::SSIM_TAPS - 1), OW = W - (rn::SSIM_TAPS - 1);
+  const dim3 grid((unsigned)((OW + rn::SSIM_TILE - 1) / rn::SSIM_TILE), (unsigned)((OH + rn::SSIM_TILE - 1) / rn::SSIM_TILE));
+  long tslot;
+  { int trc = timer_begin(st, &tslot, REFNERF_TIMER_IMAGE); if (trc) return trc; }
+  hipLaunchKernelGGL(rn::image_ssim_kernel, grid, dim3(rn::IMG_THREADS), 0, st, d_a, pitch_a, d_b, pitch_b, H, W, C, quantize_a ? 1 : 0,
+                     taps, partials, d_map);
+  HIP_TRY(hipGetLastError());
+  if (int rc = image_finalize(st, partials, (size_t)grid.x * grid.y, 1, rn::IMG_FIN_MEAN, (double)OH * OW * C, d_out)) return rc;
+  return timer_end(st, tslot);
+}
+
+int refnerf_color_correct(const double *d_img, int64_t pitch_img, const double *d_ref, int64_t pitch_ref, int32_t H, int32_t W,
+                          int32_t C, int32_t num_iters, double eps, double *d_out, double *d_warp, void *d_workspace,
+                          size_t workspace_bytes, void *stream) {
+  const char *fn = "refnerf_color_correct";
+  ImageLayout L;
+  if (C != 3) return fail(REFNERF_EINVAL, "%s: C must be 3", fn);
+  if (int rc = check_image_pair(fn, d_img, pitch_img, d_ref, pitch_ref, H, W, C, d_out, d_workspace, &L)) return rc;
+  if (num_iters < 0 || num_iters > 64) return fail(REFNERF_EINVAL, "%s: num_iters must be in [0, 64]", fn);
+  if (!std::isfinite(eps)) return fail(REFNERF_EINVAL, "%s: non-finite eps", fn);
+  if ((uintptr_t)d_warp & 7u) return fail(REFNERF_EINVAL, "%s: misaligned pointer", fn);
+  if (workspace_bytes < L.total) return fail(REFNERF_EINVAL, "%s: workspace too small (see refnerf_image_workspace_bytes)", fn);
+  hipStream_t st = (hipStream_t)stream;
+  double *warp = static_cast<double *>(d_workspace) + L.scratch, *partials = warp + 32;
+  const int64_t npix = (int64_t)H * W;
+  const dim3 apply_grid((unsigned)((npix + rn::IMG_THREADS - 1) / rn::IMG_THREADS));
+  long tslot;
+  { int trc = timer_begin(st, &tslot, REFNERF_TIMER_IMAGE); if (trc) return trc; }
+  if (num_iters == 0) {
+    hipLaunchKernelGGL(rn::cc_apply_kernel, apply_grid, dim3(rn::IMG_THREADS), 0, st, d_img, pitch_img, d_out, W, npix, (const double *)nullptr);
+    HIP_TRY(hipGetLastError());
+  }
+  for (int it = 0; it < num_iters; ++it) {
+    /* the current estimate: the input itself, then the dense output (updated in place) */
+    const double *x = it == 0 ? d_img : d_out;
+    const int64_t pitch_x = it == 0 ? pitch_img : (int64_t)W * 3;
+    hipLaunchKernelGGL(rn::cc_accum_kernel, dim3((unsigned)L.px_blocks, 3), dim3(rn::IMG_THREADS), 0, st, x, pitch_x, d_img, pitch_img,
+                       d_ref, pitch_ref, W, npix, eps, partials);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(rn::cc_solve_kernel, dim3(1), dim3(rn::IMG_THREADS), 0, st, partials, (int32_t)L.px_blocks, warp,
+                       it == num_iters - 1 ? d_warp : (double *)nullptr);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(rn::cc_apply_kernel, apply_grid, dim3(rn::IMG_THREADS), 0, st, x, pitch_x, d_out, W, npix, (const double *)warp);
+    HIP_TRY(hipGetLastError());
+  }
+  return timer_end(st, tslot);
+}
+
+int refnerf_weighted_mae(const double *d_weights, const double *d_normals, const double *d_normals_gt, int64_t n, double *d_out,
+                         void *d_workspace, size_t workspace_bytes, void *stream) {
+  const char *fn = "refnerf_weighted_mae";
+  if (!d_weights || !d_normals || !d_normals_gt || !d_out || !d_workspace) return fail(REFNERF_EINVAL, "%s: null pointer", fn);
+  if (n <= 0 || n > INT32_MAX / 3) return fail(REFNERF_EINVAL, "%s: n must be positive and 3 n below 2^31", fn);
+  if (((uintptr_t)d_weights | (uintptr_t)d_normals | (uintptr_t)d_normals_gt | (uintptr_t)d_out | (uintptr_t)d_workspace) & 7u)
+    return fail(REFNERF_EINVAL, "%s: misaligned pointer", fn);
+  const size_t blocks = (size_t)((n + rn::IMG_PIX_PER_BLOCK - 1) / rn::IMG_PIX_PER_BLOCK);
+  if (workspace_bytes < 2 * blocks * sizeof(double)) return fail(REFNERF_EINVAL, "%s: workspace too small (see refnerf_image_workspace_bytes)", fn);
+  hipStream_t st = (hipStream_t)stream;
+  double *partials = static_cast<double *>(d_workspace);
+  long tslot;
+  { int trc = timer_begin(st, &tslot, REFNERF_TIMER_IMAGE); if (trc) return trc; }
+  hipLaunchKernelGGL(rn::image_wmae_kernel, dim3((unsigned)blocks), dim3(rn::IMG_THREADS), 0, st, d_weights, d_normals, d_normals_gt, n, partials);
+  HIP_TRY(hipGetLastError());
+  if (int rc = image_finalize(st, partials, blocks, 2, rn::IMG_FIN_DEGREES, 1.0, d_out)) return rc;
+  return timer_end(st, tslot);
 }
 
 int refnerf_set_timing(int enable) {
