@@ -608,6 +608,80 @@ int refnerf_color_correct(const double *d_img, int64_t pitch_img, const double *
 int refnerf_weighted_mae(const double *d_weights, const double *d_normals, const double *d_normals_gt, int64_t n,
                          double *d_out /* [1] */, void *d_workspace, size_t workspace_bytes, void *stream);
 
+/* Validation visualisations, the reference's internal/vis.py (visualize_suite, nerf_system.py:307), on the device.
+ * Image and ray inputs are dense float32 or float64 (one `f64` flag per call: 0 = float, 1 = double); ALL arithmetic is
+ * float64, and a float32 output is rounded once, when it is written.  No entry synchronises the host, allocates or uses a
+ * float atomic: two runs are bit-identical.  eps = 2^-23 (finfo(float32).eps) throughout.
+ *
+ *   refnerf_vis_weighted_percentile   vis.weighted_percentile (vis.py:26-36, math.py:114-142).  d_order is a STABLE ascending
+ *       order of the n values (NaNs last; the caller sorts, ties in index order); the weight of the value at flat index j is
+ *       d_weights[j % n_weights], exactly as the reference indexes a [H][W] weight map by a [H][W][3] value map (NULL: all
+ *       ones), and 0 where d_nan_mask[j % n_weights] is NaN (optional: visualize_suite's `acc` at NaN distances).  Launches:
+ *       per-workgroup sums of the gathered weights (2048 per workgroup) -> their exclusive scan in index order by one lane
+ *       -> the inclusive scan acc[] -> #{acc[i] <= target_p} (integer counts) -> per percentile the reference's interp:
+ *       target = ps[p] * acc[n-1] / 100 (evaluated in float32 when target_f32 is set: the reference's torch.tensor(ps) is a
+ *       float32 tensor and wins the promotion against the 0-dim total), idx = clamp(count - 1, 0, n - 2),
+ *       m = (x[idx+1] - x[idx]) / (acc[idx+1] - acc[idx]), b = x[idx] - m acc[idx], d_out[p] = m target + b -- including the
+ *       linear extrapolation below the first knot, and NaN where all weights are 0.  n_ps in 1..8, n >= 2.  An order entry
+ *       outside [0, n) poisons the result with NaN and reads nothing out of bounds.
+ *   refnerf_vis_panels   every per-pixel panel of visualize_suite in one launch; every pointer is optional and an output is
+ *       written when it and its inputs are given.  acc' = acc, 0 where distance_mean is NaN.  matte(v) = v acc' +
+ *       bg (1 - acc') with the 8-pixel checker bg in {float32(0.8), 1}.  color / diffuse / specular: the sRGB curve when
+ *       linear_to_srgb is set.  depth_mean / depth_median: c(v) = -log(v + eps), q = nan_to_num(clip((c(v) - min(lo, hi)) /
+ *       |hi - lo|, 0, 1)) with lo = c(lohi[0] - eps), hi = c(lohi[1] + eps), colour d_table[min(int(q N), N - 1)], matted.
+ *       depth_triplet: (2 median - p5, median, p95) through c(v) = log(v + eps) alike, no table.  coords_mod:
+ *       ((origins + directions distance_mean + 1) mod 2) / 2 with the sign of the divisor, matted (NaN where the distance
+ *       is NaN, as in the reference).  normals_out[k]: matte(n / 2 + 0.5); roughness: matte(tanh(r)), roughness_channels
+ *       wide; tint_matte; color_corrected: a copy.  d_lohi_*: two doubles each, the RAW percentiles of entry 1.
+ *   refnerf_vis_cmap   visualize_cmap on n = H * W values of `channels` channels: optional curve, optional normalisation
+ *       (lo = [*d_lo +] lo_bias, hi = [*d_hi +] hi_bias, then curved), optional table (channels must be 1; output 3
+ *       channels), optional matte (d_acc), optional null colour where d_alpha == 0 (visualize_suite's ray_weights panel).
+ *   refnerf_vis_resample_rays   stepfun.resample(edges, sdist, ., use_avg=True) of n step functions (sdist [n][N+1], values
+ *       [n][N][C], weights [n][N] or NULL = ones) onto the `resolution` bins between the resolution + 1 edges d_edges:
+ *       sequential float64 cumulative sums, the reference's interp at every edge INCLUDING its extrapolation outside
+ *       [sdist[0], sdist[N]], numer / max(eps, denom).  accumulate: visualize_rays' accumulated colour and weight.
+ *       value_op: REFNERF_VIS_OP_*.  Line i goes to d_out_values + i * line_stride * resolution * C (alpha alike), so the
+ *       levels of one bundle interleave into [n][L][resolution][C].  (N + 1) * (C + 3) * 8 bytes of LDS: at most 48 KB.
+ *   refnerf_vis_ray_panel   visualize_rays' panel from the [n][L] lines: alpha / max(eps, *d_alpha_max) when d_alpha_max is
+ *       given (renormalize), rep > 0: every line rep times, one background strip per ray, the last row dropped
+ *       (n (L rep + 1) - 1 rows); rep = 0: the lines of the first n - 1 rays; out = v alpha + bg_color (1 - alpha).
+ * REFNERF_EINVAL: a missing required pointer, sizes outside the stated ranges, a workspace too small. */
+enum { REFNERF_VIS_CURVE_NONE = 0, REFNERF_VIS_CURVE_NEG_LOG = 1 /* -log(x + eps) */, REFNERF_VIS_CURVE_LOG = 2 /* log(x + eps) */ };
+enum { REFNERF_VIS_OP_NONE = 0, REFNERF_VIS_OP_CLIP01 = 1 /* clip(v, 0, 1) */, REFNERF_VIS_OP_SQRT = 2 /* sqrt(v) */ };
+#define REFNERF_VIS_MAX_PS 8
+#define REFNERF_VIS_MAX_NORMALS 4
+typedef struct refnerf_vis_panels_args {
+  int32_t H, W, f64, linear_to_srgb, table_n, roughness_channels;
+  const float *d_table;                                            /* [table_n][3] */
+  const double *d_lohi_mean, *d_lohi_median, *d_lohi_triplet;      /* [2] each */
+  const void *d_rgb, *d_acc, *d_distance_mean, *d_distance_median, *d_distance_p5, *d_distance_p95, *d_origins, *d_directions,
+      *d_normals[REFNERF_VIS_MAX_NORMALS], *d_roughness, *d_diffuse, *d_specular, *d_tint, *d_rgb_cc;
+  void *d_color, *d_acc_out, *d_color_matte, *d_depth_mean, *d_depth_median, *d_depth_triplet, *d_coords_mod,
+      *d_normals_out[REFNERF_VIS_MAX_NORMALS], *d_roughness_out, *d_diffuse_out, *d_diffuse_matte, *d_specular_out,
+      *d_specular_matte, *d_tint_matte, *d_color_corrected;
+} refnerf_vis_panels_args;
+typedef struct refnerf_vis_cmap_args {
+  int32_t H, W, channels, f64 /* d_values, d_acc */, out_f64, curve, normalise, table_n;
+  double lo_bias, hi_bias, null_color[3];
+  const void *d_values, *d_acc /* [H][W] or NULL: no matte */;
+  const double *d_lo, *d_hi /* device scalars or NULL */, *d_alpha /* [H][W] or NULL */;
+  const float *d_table;
+  void *d_out;                                                     /* [H][W][table ? 3 : channels] */
+} refnerf_vis_cmap_args;
+size_t refnerf_vis_percentile_workspace_bytes(int64_t n);
+int refnerf_vis_weighted_percentile(const void *d_values, int32_t values_f64, const void *d_weights, int32_t weights_f64,
+                                    int64_t n_weights, const void *d_nan_mask, const int64_t *d_order, int64_t n,
+                                    const double *ps /* host */, int32_t n_ps, int32_t target_f32, double *d_out /* [n_ps] */,
+                                    void *d_workspace, size_t workspace_bytes, void *stream);
+int refnerf_vis_panels(const refnerf_vis_panels_args *args, void *stream);
+int refnerf_vis_cmap(const refnerf_vis_cmap_args *args, void *stream);
+int refnerf_vis_resample_rays(const void *d_sdist, const void *d_values, const void *d_weights, int32_t f64, int32_t n, int32_t N,
+                              int32_t C, const double *d_edges, int32_t resolution, int32_t accumulate, int32_t value_op,
+                              int64_t line_stride, double *d_out_values, double *d_out_alpha, void *stream);
+int refnerf_vis_ray_panel(const double *d_lines_values, const double *d_lines_alpha, int32_t n, int32_t L, int32_t resolution,
+                          int32_t C, int32_t rep, double bg_color, const double *d_alpha_max, double *d_out_vis,
+                          double *d_out_alpha, void *stream);
+
 /* Total duration (ms) and count of the `refnerf_level_forward` kernels launched
  * since refnerf_set_timing(1), from HIP event pairs on the launch stream.
  * Used by bench.py for the roofline line. */

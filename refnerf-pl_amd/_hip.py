@@ -100,6 +100,32 @@ class NoisyRaysArgs(C.Structure):
         ("d_" + n, _FP) for n in RAY_FIELDS] + [("d_out_" + n, _FP) for n in RAY_FIELDS]
 
 
+VIS_CURVES = {"none": 0, "neg_log": 1, "log": 2}      # REFNERF_VIS_CURVE_*
+VIS_OPS = {"none": 0, "clip01": 1, "sqrt": 2}         # REFNERF_VIS_OP_*
+VIS_MAX_PS, VIS_MAX_NORMALS = 8, 4
+VIS_PANEL_INPUTS = ("d_rgb", "d_acc", "d_distance_mean", "d_distance_median", "d_distance_p5", "d_distance_p95", "d_origins",
+                    "d_directions")
+VIS_PANEL_INPUTS_2 = ("d_roughness", "d_diffuse", "d_specular", "d_tint", "d_rgb_cc")
+VIS_PANEL_OUTPUTS = ("d_color", "d_acc_out", "d_color_matte", "d_depth_mean", "d_depth_median", "d_depth_triplet", "d_coords_mod")
+VIS_PANEL_OUTPUTS_2 = ("d_roughness_out", "d_diffuse_out", "d_diffuse_matte", "d_specular_out", "d_specular_matte", "d_tint_matte",
+                       "d_color_corrected")
+
+
+class VisPanelsArgs(C.Structure):
+    """refnerf_vis_panels_args."""
+    _fields_ = [(n, C.c_int32) for n in ("H", "W", "f64", "linear_to_srgb", "table_n", "roughness_channels")] + [
+        (n, _FP) for n in ("d_table", "d_lohi_mean", "d_lohi_median", "d_lohi_triplet") + VIS_PANEL_INPUTS] + [
+        ("d_normals", _FP * VIS_MAX_NORMALS)] + [(n, _FP) for n in VIS_PANEL_INPUTS_2 + VIS_PANEL_OUTPUTS] + [
+        ("d_normals_out", _FP * VIS_MAX_NORMALS)] + [(n, _FP) for n in VIS_PANEL_OUTPUTS_2]
+
+
+class VisCmapArgs(C.Structure):
+    """refnerf_vis_cmap_args."""
+    _fields_ = [(n, C.c_int32) for n in ("H", "W", "channels", "f64", "out_f64", "curve", "normalise", "table_n")] + [
+        ("lo_bias", C.c_double), ("hi_bias", C.c_double), ("null_color", C.c_double * 3)] + [
+        (n, _FP) for n in ("d_values", "d_acc", "d_lo", "d_hi", "d_alpha", "d_table", "d_out")]
+
+
 class HipLibraryError(RuntimeError):
     pass
 
@@ -182,6 +208,14 @@ def lib():
         L.refnerf_color_correct.argtypes = [_FP, C.c_int64, _FP, C.c_int64] + [C.c_int32] * 4 + [C.c_double, _FP, _FP, _FP,
                                                                                                   C.c_size_t, _FP]
         L.refnerf_weighted_mae.argtypes = [_FP, _FP, _FP, C.c_int64, _FP, _FP, C.c_size_t, _FP]
+        L.refnerf_vis_percentile_workspace_bytes.restype = C.c_size_t
+        L.refnerf_vis_percentile_workspace_bytes.argtypes = [C.c_int64]
+        L.refnerf_vis_weighted_percentile.argtypes = [_FP, C.c_int32, _FP, C.c_int32, C.c_int64, _FP, _FP, C.c_int64,
+                                                      C.POINTER(C.c_double), C.c_int32, C.c_int32, _FP, _FP, C.c_size_t, _FP]
+        L.refnerf_vis_panels.argtypes = [C.POINTER(VisPanelsArgs), _FP]
+        L.refnerf_vis_cmap.argtypes = [C.POINTER(VisCmapArgs), _FP]
+        L.refnerf_vis_resample_rays.argtypes = [_FP, _FP, _FP] + [C.c_int32] * 4 + [_FP] + [C.c_int32] * 3 + [C.c_int64, _FP, _FP, _FP]
+        L.refnerf_vis_ray_panel.argtypes = [_FP, _FP] + [C.c_int32] * 5 + [C.c_double, _FP, _FP, _FP, _FP]
         L.refnerf_get_timing.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_int64)]
         L.refnerf_get_timing_family.argtypes = [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
         if L.refnerf_abi_version() != ABI_VERSION:
@@ -783,6 +817,166 @@ def weighted_mae(weights, normals, normals_gt, workspace=None):
     out = torch.empty(1, dtype=torch.float64, device=w.device)
     check(lib().refnerf_weighted_mae(ptr(w), ptr(a), ptr(b), n, ptr(out), ptr(ws), ws.numel() * 8, stream_ptr()))
     return out[0]
+
+
+# ---- validation visualisations (refnerf_vis_*): raw bindings; refnerf_pl_amd.vis is the interface ----
+VIS_LAUNCHES = 0      # kernel launches of the vis entries since import (scripts/time_vis.py reads the difference)
+
+
+def _vis_f64(t, what):
+    """1 for a float64, 0 for a float32 dense device tensor"""
+    if not (t.is_cuda and t.is_contiguous() and t.dtype in (torch.float32, torch.float64)):
+        raise ValueError(f"{what}: a contiguous float32 or float64 device tensor is required")
+    return int(t.dtype == torch.float64)
+
+
+def vis_percentile_workspace(n: int, device) -> torch.Tensor:
+    nbytes = int(lib().refnerf_vis_percentile_workspace_bytes(int(n)))
+    if nbytes == 0:
+        raise ValueError(f"weighted_percentile: {n} values (at least two are required, fewer than 2^31)")
+    return torch.empty(nbytes // 8, dtype=torch.float64, device=device)
+
+
+def vis_weighted_percentile(values, weights, order, ps, target_f32=True, nan_mask=None, workspace=None):
+    """refnerf_vis_weighted_percentile: a float64 device tensor [len(ps)].  `values` flat, `order` its stable ascending
+    order (int64), `weights` flat or None (all ones), `nan_mask` of the weights' shape and type or None."""
+    global VIS_LAUNCHES
+    n = values.numel()
+    ws = vis_percentile_workspace(n, values.device) if workspace is None else workspace
+    if not (order.is_cuda and order.dtype == torch.int64 and order.is_contiguous() and order.numel() == n):
+        raise ValueError("weighted_percentile: the order must be a contiguous int64 device tensor of the values' length")
+    wf = 0 if weights is None else _vis_f64(weights, "weighted_percentile weights")
+    if nan_mask is not None and (weights is None or nan_mask.dtype != weights.dtype or nan_mask.numel() != weights.numel()
+                                 or _vis_f64(nan_mask, "weighted_percentile nan_mask") != wf):
+        raise ValueError("weighted_percentile: the NaN mask must have the weights' type and size")
+    ps = [float(p) for p in ps]
+    out = torch.empty(len(ps), dtype=torch.float64, device=values.device)
+    check(lib().refnerf_vis_weighted_percentile(ptr(values), _vis_f64(values, "weighted_percentile values"), ptr(weights), wf,
+                                                0 if weights is None else weights.numel(), ptr(nan_mask), ptr(order), n,
+                                                (C.c_double * len(ps))(*ps), len(ps), int(bool(target_f32)), ptr(out), ptr(ws),
+                                                ws.numel() * 8, stream_ptr()))
+    VIS_LAUNCHES += 5
+    return out
+
+
+def vis_panels(H, W, dtype, linear_to_srgb, table, inputs, outputs, lohi=(None, None, None), normals=(), roughness_channels=1):
+    """refnerf_vis_panels.  `inputs` maps the names of VIS_PANEL_INPUTS* (without 'd_') to dense device tensors of `dtype`,
+    `outputs` names the panels wanted (VIS_PANEL_OUTPUTS* without 'd_'); `normals` is a list of up to four normal maps.
+    Returns {name: tensor} plus 'normals_out': [tensors]."""
+    global VIS_LAUNCHES
+    a = VisPanelsArgs()
+    a.H, a.W, a.f64, a.linear_to_srgb, a.roughness_channels = int(H), int(W), int(dtype == torch.float64), int(bool(linear_to_srgb)), int(roughness_channels)
+    dev = None
+    for name, t in inputs.items():
+        if "d_" + name not in VIS_PANEL_INPUTS + VIS_PANEL_INPUTS_2:
+            raise KeyError(name)
+        if t.dtype != dtype or _vis_f64(t, "vis_panels " + name) != a.f64:
+            raise ValueError(f"vis_panels: {name} is not of the panels' type")
+        width = 1 if name in ("acc", "distance_mean", "distance_median", "distance_p5", "distance_p95") else (
+            roughness_channels if name == "roughness" else 3)
+        if t.numel() != H * W * width:
+            raise ValueError(f"vis_panels: {name} has {t.numel()} elements, not {H} x {W} x {width}")
+        setattr(a, "d_" + name, t.data_ptr())
+        dev = t.device
+    if len(normals) > VIS_MAX_NORMALS:
+        raise ValueError("vis_panels: at most four normal maps per call")
+    if table is not None:
+        if not (table.is_cuda and table.dtype == torch.float32 and table.is_contiguous() and table.dim() == 2 and table.shape[1] == 3):
+            raise ValueError("vis_panels: the colour table must be a contiguous float32 device tensor [N, 3]")
+        a.d_table, a.table_n = table.data_ptr(), int(table.shape[0])
+    for field, t in zip(("d_lohi_mean", "d_lohi_median", "d_lohi_triplet"), lohi):
+        if t is not None:
+            if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.numel() >= 2):
+                raise ValueError("vis_panels: the percentile pairs are float64 device tensors [2]")
+            setattr(a, field, t.data_ptr())
+    out = {}
+    widths = {"acc_out": None, "roughness_out": roughness_channels}
+    for name in outputs:
+        if "d_" + name not in VIS_PANEL_OUTPUTS + VIS_PANEL_OUTPUTS_2:
+            raise KeyError(name)
+        w = widths.get(name, 3)
+        out[name] = torch.empty((H, W) if w is None else (H, W, w), dtype=dtype, device=dev)
+        setattr(a, "d_" + name, out[name].data_ptr())
+    out["normals_out"] = []
+    for k, t in enumerate(normals):
+        if t.dtype != dtype or _vis_f64(t, "vis_panels normals") != a.f64 or t.numel() != H * W * 3:
+            raise ValueError("vis_panels: a normal map is not [H, W, 3] of the panels' type")
+        o = torch.empty((H, W, 3), dtype=dtype, device=dev)
+        a.d_normals[k], a.d_normals_out[k] = t.data_ptr(), o.data_ptr()
+        out["normals_out"].append(o)
+    check(lib().refnerf_vis_panels(C.byref(a), stream_ptr()))
+    VIS_LAUNCHES += 1
+    return out
+
+
+def vis_cmap(values, H, W, channels, out_dtype, curve="none", normalise=False, d_lo=None, lo_bias=0.0, d_hi=None, hi_bias=0.0,
+             table=None, acc=None, alpha=None, null_color=(1.0, 0.0, 0.0)):
+    """refnerf_vis_cmap: [H, W, 3 with a table, else channels] of `out_dtype` (float32 or float64)."""
+    global VIS_LAUNCHES
+    a = VisCmapArgs()
+    a.H, a.W, a.channels, a.f64 = int(H), int(W), int(channels), _vis_f64(values, "vis_cmap values")
+    a.out_f64, a.curve, a.normalise = int(out_dtype == torch.float64), VIS_CURVES[curve], int(bool(normalise))
+    a.lo_bias, a.hi_bias = float(lo_bias), float(hi_bias)
+    a.null_color[0], a.null_color[1], a.null_color[2] = (float(c) for c in null_color)
+    if values.numel() != H * W * channels:
+        raise ValueError("vis_cmap: the values are not [H, W, channels]")
+    a.d_values = values.data_ptr()
+    if acc is not None:
+        if acc.dtype != values.dtype or _vis_f64(acc, "vis_cmap acc") != a.f64 or acc.numel() != H * W:
+            raise ValueError("vis_cmap: acc must be [H, W] of the values' type")
+        a.d_acc = acc.data_ptr()
+    for field, t, m in (("d_lo", d_lo, 1), ("d_hi", d_hi, 1), ("d_alpha", alpha, H * W)):
+        if t is not None:
+            if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.numel() >= m):
+                raise ValueError(f"vis_cmap: {field} must be a float64 device tensor")
+            setattr(a, field, t.data_ptr())
+    if table is not None:
+        if not (table.is_cuda and table.dtype == torch.float32 and table.is_contiguous() and table.dim() == 2 and table.shape[1] == 3):
+            raise ValueError("vis_cmap: the colour table must be a contiguous float32 device tensor [N, 3]")
+        a.d_table, a.table_n = table.data_ptr(), int(table.shape[0])
+    out = torch.empty((H, W, 3 if table is not None else channels), dtype=out_dtype, device=values.device)
+    a.d_out = out.data_ptr()
+    check(lib().refnerf_vis_cmap(C.byref(a), stream_ptr()))
+    VIS_LAUNCHES += 1
+    return out
+
+
+def vis_resample_rays(sdist, values, weights, edges, out_values, out_alpha, level, accumulate=False, value_op="none"):
+    """refnerf_vis_resample_rays for one level: sdist [n, N+1], values [n, N, C], weights [n, N] or None, edges float64
+    [resolution + 1]; writes out_values[:, level] of [n, L, resolution, C] and out_alpha[:, level] of [n, L, resolution]."""
+    global VIS_LAUNCHES
+    f64 = _vis_f64(sdist, "vis_resample_rays sdist")
+    n, N, Cn = values.shape
+    if _vis_f64(values, "vis_resample_rays values") != f64 or (weights is not None and _vis_f64(weights, "vis_resample_rays weights") != f64):
+        raise ValueError("vis_resample_rays: sdist, values and weights must be of one type")
+    if tuple(sdist.shape) != (n, N + 1) or (weights is not None and tuple(weights.shape) != (n, N)):
+        raise ValueError("vis_resample_rays: sdist must be [n, N + 1] and weights [n, N] for values [n, N, C]")
+    res = edges.numel() - 1
+    L = out_values.shape[1]
+    if not (edges.is_cuda and edges.dtype == torch.float64 and edges.is_contiguous() and tuple(out_values.shape) == (n, L, res, Cn)
+            and tuple(out_alpha.shape) == (n, L, res) and out_values.dtype == torch.float64 and out_alpha.dtype == torch.float64
+            and out_values.is_contiguous() and out_alpha.is_contiguous() and 0 <= level < L):
+        raise ValueError("vis_resample_rays: edges [resolution + 1] and the outputs [n, L, resolution(, C)] must be dense float64")
+    check(lib().refnerf_vis_resample_rays(ptr(sdist), ptr(values), ptr(weights), f64, n, N, Cn, ptr(edges), res, int(bool(accumulate)),
+                                          VIS_OPS[value_op], L, C.c_void_p(out_values.data_ptr() + level * res * Cn * 8),
+                                          C.c_void_p(out_alpha.data_ptr() + level * res * 8), stream_ptr()))
+    VIS_LAUNCHES += 1
+
+
+def vis_ray_panel(lines_values, lines_alpha, rep, bg_color, alpha_max=None):
+    """refnerf_vis_ray_panel: (panel [rows, resolution, C], alpha [rows, resolution]) in float64 from the lines
+    [n, L, resolution, C] / [n, L, resolution]; rep = 0 keeps the lines of the first n - 1 rays untiled."""
+    global VIS_LAUNCHES
+    n, L, res, Cn = lines_values.shape
+    rows = n * (L * rep + 1) - 1 if rep > 0 else (n - 1) * L
+    vis = torch.empty((rows, res, Cn), dtype=torch.float64, device=lines_values.device)
+    alpha = torch.empty((rows, res), dtype=torch.float64, device=lines_values.device)
+    if alpha_max is not None and not (alpha_max.is_cuda and alpha_max.dtype == torch.float64 and alpha_max.numel() == 1):
+        raise ValueError("vis_ray_panel: alpha_max must be a float64 device scalar")
+    check(lib().refnerf_vis_ray_panel(ptr(lines_values), ptr(lines_alpha), n, L, res, Cn, int(rep), float(bg_color), ptr(alpha_max),
+                                      ptr(vis), ptr(alpha), stream_ptr()))
+    VIS_LAUNCHES += 1
+    return vis, alpha
 
 
 def set_timing(enable: bool):

@@ -34,6 +34,7 @@
 #include "refnerf_regularisers.h"
 #include "refnerf_proposal.h"
 #include "refnerf_image.h"
+#include "refnerf_vis.h"
 #include "refnerf_pack_common.h"
 #include "refnerf_sq_host.h"
 #include "refnerf_sq_layout.h"
@@ -1597,6 +1598,128 @@ int refnerf_weighted_mae(const double *d_weights, const double *d_normals, const
   HIP_TRY(hipGetLastError());
   if (int rc = image_finalize(st, partials, blocks, 2, rn::IMG_FIN_DEGREES, 1.0, d_out)) return rc;
   return timer_end(st, tslot);
+}
+
+/* ---- validation visualisations (refnerf_vis.h) ---- */
+namespace {
+bool vis_misaligned(const void *p, int f64) { return ((uintptr_t)p & (f64 ? 7u : 3u)) != 0; }
+}  // namespace
+
+size_t refnerf_vis_percentile_workspace_bytes(int64_t n) {
+  if (n < 2 || n > INT32_MAX) return 0;
+  const size_t blocks = (size_t)((n + rn::VIS_SCAN_BLOCK - 1) / rn::VIS_SCAN_BLOCK);
+  return ((size_t)n + 2 * blocks + REFNERF_VIS_MAX_PS) * sizeof(double);
+}
+
+int refnerf_vis_weighted_percentile(const void *d_values, int32_t values_f64, const void *d_weights, int32_t weights_f64,
+                                    int64_t n_weights, const void *d_nan_mask, const int64_t *d_order, int64_t n, const double *ps,
+                                    int32_t n_ps, int32_t target_f32, double *d_out, void *d_workspace, size_t workspace_bytes,
+                                    void *stream) {
+  const char *fn = "refnerf_vis_weighted_percentile";
+  if (!d_values || !d_order || !ps || !d_out || !d_workspace) return fail(REFNERF_EINVAL, "%s: null pointer", fn);
+  if (n < 2 || n > INT32_MAX) return fail(REFNERF_EINVAL, "%s: n must be in [2, 2^31) (the interpolation needs two knots)", fn);
+  if (n_ps < 1 || n_ps > REFNERF_VIS_MAX_PS) return fail(REFNERF_EINVAL, "%s: n_ps must be in [1, 8]", fn);
+  if (d_weights && (n_weights < 1 || n_weights > n)) return fail(REFNERF_EINVAL, "%s: n_weights must be in [1, n]", fn);
+  if (d_nan_mask && !d_weights) return fail(REFNERF_EINVAL, "%s: d_nan_mask needs d_weights", fn);
+  if (vis_misaligned(d_values, values_f64) || vis_misaligned(d_weights, weights_f64) || vis_misaligned(d_nan_mask, weights_f64) ||
+      (((uintptr_t)d_order | (uintptr_t)d_out | (uintptr_t)d_workspace) & 7u))
+    return fail(REFNERF_EINVAL, "%s: misaligned pointer", fn);
+  if (workspace_bytes < refnerf_vis_percentile_workspace_bytes(n))
+    return fail(REFNERF_EINVAL, "%s: workspace too small (see refnerf_vis_percentile_workspace_bytes)", fn);
+  rn::VisPctArgs a{};
+  a.values = d_values; a.weights = d_weights; a.nan_mask = d_nan_mask; a.order = d_order;
+  a.n = n; a.n_weights = d_weights ? n_weights : 1;
+  a.values_f64 = values_f64 ? 1 : 0; a.weights_f64 = weights_f64 ? 1 : 0; a.n_ps = n_ps; a.target_f32 = target_f32 ? 1 : 0;
+  for (int p = 0; p < n_ps; ++p) a.ps[p] = ps[p];
+  a.n_blocks = (n + rn::VIS_SCAN_BLOCK - 1) / rn::VIS_SCAN_BLOCK;
+  a.acc = static_cast<double *>(d_workspace);
+  a.block_sums = a.acc + n;
+  a.block_offs = a.block_sums + a.n_blocks;
+  a.counts = reinterpret_cast<unsigned long long *>(a.block_offs + a.n_blocks);
+  a.out = d_out;
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid((unsigned)a.n_blocks), block(rn::VIS_THREADS);
+  hipLaunchKernelGGL(rn::vis_scan_partial_kernel, grid, block, 0, st, a);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(rn::vis_scan_blocks_kernel, dim3(1), dim3(64), 0, st, a);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(rn::vis_scan_final_kernel, grid, block, 0, st, a);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(rn::vis_pct_count_kernel, grid, block, 0, st, a);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(rn::vis_pct_final_kernel, dim3(1), dim3(64), 0, st, a);
+  HIP_TRY(hipGetLastError());
+  return REFNERF_OK;
+}
+
+int refnerf_vis_panels(const refnerf_vis_panels_args *args, void *stream) {
+  const char *fn = "refnerf_vis_panels";
+  if (!args) return fail(REFNERF_EINVAL, "%s: null pointer", fn);
+  if (args->H <= 0 || args->W <= 0 || (int64_t)args->H * args->W * 3 > INT32_MAX)
+    return fail(REFNERF_EINVAL, "%s: H and W must be positive and 3 H W below 2^31", fn);
+  if (args->d_table && args->table_n < 1) return fail(REFNERF_EINVAL, "%s: table_n must be positive", fn);
+  if (args->d_roughness && (args->roughness_channels < 1 || args->roughness_channels > 4))
+    return fail(REFNERF_EINVAL, "%s: roughness_channels must be in [1, 4]", fn);
+  if ((args->d_depth_mean || args->d_depth_median) && !(args->d_table && args->d_acc))
+    return fail(REFNERF_EINVAL, "%s: the depth panels need d_table and d_acc", fn);
+  const int64_t npix = (int64_t)args->H * args->W;
+  hipLaunchKernelGGL(rn::vis_panels_kernel, dim3((unsigned)((npix + rn::VIS_THREADS - 1) / rn::VIS_THREADS)), dim3(rn::VIS_THREADS), 0,
+                     (hipStream_t)stream, *args);
+  HIP_TRY(hipGetLastError());
+  return REFNERF_OK;
+}
+
+int refnerf_vis_cmap(const refnerf_vis_cmap_args *args, void *stream) {
+  const char *fn = "refnerf_vis_cmap";
+  if (!args || !args->d_values || !args->d_out) return fail(REFNERF_EINVAL, "%s: null pointer", fn);
+  if (args->H <= 0 || args->W <= 0 || (int64_t)args->H * args->W * 4 > INT32_MAX)
+    return fail(REFNERF_EINVAL, "%s: H and W must be positive and 4 H W below 2^31", fn);
+  if (args->channels < 1 || args->channels > 4) return fail(REFNERF_EINVAL, "%s: channels must be in [1, 4]", fn);
+  if (args->d_table && (args->channels != 1 || args->table_n < 1))
+    return fail(REFNERF_EINVAL, "%s: a table needs one channel and table_n >= 1", fn);
+  if (args->curve < REFNERF_VIS_CURVE_NONE || args->curve > REFNERF_VIS_CURVE_LOG) return fail(REFNERF_EINVAL, "%s: unknown curve", fn);
+  const int64_t npix = (int64_t)args->H * args->W;
+  hipLaunchKernelGGL(rn::vis_cmap_kernel, dim3((unsigned)((npix + rn::VIS_THREADS - 1) / rn::VIS_THREADS)), dim3(rn::VIS_THREADS), 0,
+                     (hipStream_t)stream, *args);
+  HIP_TRY(hipGetLastError());
+  return REFNERF_OK;
+}
+
+int refnerf_vis_resample_rays(const void *d_sdist, const void *d_values, const void *d_weights, int32_t f64, int32_t n, int32_t N,
+                              int32_t C, const double *d_edges, int32_t resolution, int32_t accumulate, int32_t value_op,
+                              int64_t line_stride, double *d_out_values, double *d_out_alpha, void *stream) {
+  const char *fn = "refnerf_vis_resample_rays";
+  if (!d_sdist || !d_values || !d_edges || !d_out_values || !d_out_alpha) return fail(REFNERF_EINVAL, "%s: null pointer", fn);
+  if (n < 1 || N < 1 || C < 1 || C > 4 || resolution < 1 || line_stride < 1)
+    return fail(REFNERF_EINVAL, "%s: n, N, resolution and line_stride must be positive and C in [1, 4]", fn);
+  const size_t lds = (size_t)(N + 1) * (C + 3) * sizeof(double);
+  if (lds > 48 * 1024) return fail(REFNERF_EINVAL, "%s: (N + 1) (C + 3) doubles must fit 48 KB of LDS", fn);
+  if ((int64_t)n * line_stride * resolution * C > INT32_MAX) return fail(REFNERF_EINVAL, "%s: the lines exceed 2^31 elements", fn);
+  if (value_op < REFNERF_VIS_OP_NONE || value_op > REFNERF_VIS_OP_SQRT) return fail(REFNERF_EINVAL, "%s: unknown value_op", fn);
+  rn::VisResampleArgs a{};
+  a.sdist = d_sdist; a.values = d_values; a.weights = d_weights; a.edges = d_edges;
+  a.out_values = d_out_values; a.out_alpha = d_out_alpha; a.line_stride = line_stride;
+  a.f64 = f64 ? 1 : 0; a.n = n; a.N = N; a.C = C; a.resolution = resolution; a.accumulate = accumulate ? 1 : 0; a.value_op = value_op;
+  hipLaunchKernelGGL(rn::vis_resample_kernel, dim3((unsigned)n), dim3(rn::VIS_THREADS), lds, (hipStream_t)stream, a);
+  HIP_TRY(hipGetLastError());
+  return REFNERF_OK;
+}
+
+int refnerf_vis_ray_panel(const double *d_lines_values, const double *d_lines_alpha, int32_t n, int32_t L, int32_t resolution,
+                          int32_t C, int32_t rep, double bg_color, const double *d_alpha_max, double *d_out_vis, double *d_out_alpha,
+                          void *stream) {
+  const char *fn = "refnerf_vis_ray_panel";
+  if (!d_lines_values || !d_lines_alpha || !d_out_vis || !d_out_alpha) return fail(REFNERF_EINVAL, "%s: null pointer", fn);
+  if (n < 1 || L < 1 || resolution < 1 || C < 1 || C > 4 || rep < 0) return fail(REFNERF_EINVAL, "%s: bad sizes", fn);
+  const int64_t rows = rep > 0 ? (int64_t)n * ((int64_t)L * rep + 1) - 1 : (int64_t)(n - 1) * L;
+  if (rows * resolution * C > INT32_MAX) return fail(REFNERF_EINVAL, "%s: the panel exceeds 2^31 elements", fn);
+  if (rows == 0) return REFNERF_OK;
+  const int64_t npix = rows * resolution;
+  hipLaunchKernelGGL(rn::vis_ray_panel_kernel, dim3((unsigned)((npix + rn::VIS_THREADS - 1) / rn::VIS_THREADS)), dim3(rn::VIS_THREADS), 0,
+                     (hipStream_t)stream, d_lines_values, d_lines_alpha, L, resolution, C, rep, rows, bg_color, d_alpha_max, d_out_vis,
+                     d_out_alpha);
+  HIP_TRY(hipGetLastError());
+  return REFNERF_OK;
 }
 
 int refnerf_set_timing(int enable) {
