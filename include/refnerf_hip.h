@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define REFNERF_ABI_VERSION 11  /* v11: refnerf_level_image (which weight image a level configuration expects as d_packed) + the library remembers the kind of every image it packs and refuses a mismatching d_packed; v10: REFNERF_IMAGE_F16X2_TRAIN + REFNERF_ACT_SQ (training levels of REFNERF_PREC_F16X2 on the eval kernel's skeleton: d_packed of refnerf_level_forward_train / refnerf_level_backward is the train image then); v9: REFNERF_ACT_F16X2 (split-f16 ACT / DELTA formats of the split-f16 training chains), refnerf_activations_format; v8: cfg.ipe_groups, refnerf_pack_weights_basis (general IPE bases: icosahedron); v7: REFNERF_PREC_F16X2 (split-operand f16: the parity-grade 16-bit inference mode); v6: cfg.dir_enc (REFNERF_DIRENC_*), cfg.raydist (REFNERF_RAYDIST_*), cfg.disable_integration; v5: refnerf_render_rays, REFNERF_PREC_F16, refnerf_get_timing_family, refnerf_losses_forward / _backward; v4: cfg.wgrad_mode, refnerf_level_saved.activations_format, bf16-chain training modes */
+#define REFNERF_ABI_VERSION 11  /* (additive since v11, no layout changed: refnerf_level_forward_ex / refnerf_level_forward_train_ex + refnerf_level_out_extra, and d_sdist_in = d_weights_in = NULL for the initial step function in all four level-forward entries) v11:refnerf_level_image (which weight image a level configuration expects as d_packed) + the library remembers the kind of every image it packs and refuses a mismatching d_packed; v10: REFNERF_IMAGE_F16X2_TRAIN + REFNERF_ACT_SQ (training levels of REFNERF_PREC_F16X2 on the eval kernel's skeleton: d_packed of refnerf_level_forward_train / refnerf_level_backward is the train image then); v9: REFNERF_ACT_F16X2 (split-f16 ACT / DELTA formats of the split-f16 training chains), refnerf_activations_format; v8: cfg.ipe_groups, refnerf_pack_weights_basis (general IPE bases: icosahedron); v7: REFNERF_PREC_F16X2 (split-operand f16: the parity-grade 16-bit inference mode); v6: cfg.dir_enc (REFNERF_DIRENC_*), cfg.raydist (REFNERF_RAYDIST_*), cfg.disable_integration; v5: refnerf_render_rays, REFNERF_PREC_F16, refnerf_get_timing_family, refnerf_losses_forward / _backward; v4: cfg.wgrad_mode, refnerf_level_saved.activations_format, bf16-chain training modes */
 #define REFNERF_NUM_PARAMS 1110158 /* canonical fp32 blob, nerf_mlp.* state_dict order */
 
 enum {
@@ -201,6 +201,17 @@ typedef struct refnerf_level_out {
   double *d_r_percentiles;  /* [R,3] float64: 5 / 50 / 95 (math.py:133-135) */
 } refnerf_level_out;
 
+/* Two more optional per-ray outputs of a level (NULL = not stored), in the layout Model.__call__ hands on, so that no copy or
+ * reduction kernel runs behind the level.  A struct of its own, taken by the _ex entries below: refnerf_level_out keeps its
+ * layout, and callers compiled against it keep working. */
+typedef struct refnerf_level_out_extra {
+  double *d_r_percentiles_soa; /* [3,R] float64: percentile p of ray r at [p * R + r] INSTEAD of refnerf_level_out.d_r_percentiles
+                                  (which is then not written): the three rows are the reference's distance_percentile_5 /
+                                  distance_median / distance_percentile_95 (render.py:240-247) without a strided copy each */
+  float *d_r_rgb_fg;           /* [R,3] sum_i w_i rgb_i: d_r_rgb before the background term and the render-time sRGB curve --
+                                  `final_rgb` of the vis rays (models.py:308-312) */
+} refnerf_level_out_extra;
+
 /* Library / device probe.  refnerf_device_ok() returns REFNERF_OK only when
  * the current HIP device is gfx950. */
 int refnerf_abi_version(void);
@@ -233,11 +244,21 @@ int refnerf_pack_weights_basis(const float *d_params, const float *d_basis, int 
  * (models.py:162-306): resample (stepfun.py:209-258) -> s_to_t (coord.py:96-98)
  * -> cast_rays (render.py:105-129) -> MLP.__call__ (models.py:533-750) ->
  * compute_alpha_weights (render.py:132-149) -> volumetric_rendering
- * (render.py:152-254).  d_sdist_in [R,n_in+1], d_weights_in [R,n_in]. */
+ * (render.py:152-254).  d_sdist_in [R,n_in+1], d_weights_in [R,n_in].
+ * d_sdist_in == NULL && d_weights_in == NULL with cfg->n_in == 1 is the step function every Model.__call__ starts
+ * from (models.py:153-157): knots cfg->s_near, cfg->s_far, weight 1 on every ray.  Nothing is read for it and the
+ * resampler takes its closed form, sample centre k = s_near + u_k (s_far - s_near): the same bits as the explicit
+ * tensors give (the softmax of one logit is 1, the CDF {0, 1}).  Also in refnerf_level_forward_train and the _ex entries.
+ * REFNERF_EINVAL: one of the two pointers NULL and the other not, NULL with n_in != 1, NULL with s_far <= s_near. */
 int refnerf_level_forward(const void *d_packed, const refnerf_level_cfg *cfg,
                           const refnerf_rays *rays, int32_t R,
                           const float *d_sdist_in, const float *d_weights_in,
                           const refnerf_level_out *out, void *stream);
+/* The same launch with the outputs of refnerf_level_out_extra as well (`extra` NULL: exactly refnerf_level_forward). */
+int refnerf_level_forward_ex(const void *d_packed, const refnerf_level_cfg *cfg,
+                             const refnerf_rays *rays, int32_t R,
+                             const float *d_sdist_in, const float *d_weights_in,
+                             const refnerf_level_out *out, const refnerf_level_out_extra *extra, void *stream);
 
 /* ---- training (the autograd graph of the same level) ----
  * With cfg->training = 1 (f32 precision mode) refnerf_level_forward also emits
@@ -303,6 +324,11 @@ int refnerf_level_forward_train(const void *d_packed, const refnerf_level_cfg *c
                                 const float *d_sdist_in, const float *d_weights_in,
                                 const refnerf_level_out *out, void *d_activations,
                                 size_t activations_bytes, void *stream);
+int refnerf_level_forward_train_ex(const void *d_packed, const refnerf_level_cfg *cfg,
+                                   const refnerf_rays *rays, int32_t R,
+                                   const float *d_sdist_in, const float *d_weights_in,
+                                   const refnerf_level_out *out, const refnerf_level_out_extra *extra, void *d_activations,
+                                   size_t activations_bytes, void *stream);   /* refnerf_level_forward_train + refnerf_level_out_extra */
 
 /* Scratch of refnerf_level_backward (per-layer output gradients + split-K partials; 17 KB per ray-sample).
  * refnerf_level_backward: d_packed is the REFNERF_PREC_F32 image of refnerf_pack_weights; cfg->precision selects the

@@ -55,6 +55,14 @@ class LevelOut(C.Structure):
     _fields_ = [(n, _FP) for n in OUT_FIELDS]
 
 
+OUT_EXTRA_FIELDS = ("d_r_percentiles_soa", "d_r_rgb_fg")
+
+
+class LevelOutExtra(C.Structure):
+    """refnerf_level_out_extra: the two per-ray outputs of the _ex level entries."""
+    _fields_ = [(n, _FP) for n in OUT_EXTRA_FIELDS]
+
+
 class LevelSaved(C.Structure):
     _fields_ = [(n, _FP) for n in ("d_sdist", "d_density", "d_rgb", "d_weights", "d_activations")] + [
         ("activations_format", C.c_int32)]
@@ -158,6 +166,8 @@ def lib():
         L.refnerf_pack_weights_basis.argtypes = [_FP, _FP, C.c_int, _FP, C.c_int, _FP]
         L.refnerf_level_forward.argtypes = [_FP, C.POINTER(LevelCfg), C.POINTER(RaysStruct), C.c_int32,
                                             _FP, _FP, C.POINTER(LevelOut), _FP]
+        L.refnerf_level_forward_ex.argtypes = [_FP, C.POINTER(LevelCfg), C.POINTER(RaysStruct), C.c_int32,
+                                               _FP, _FP, C.POINTER(LevelOut), C.POINTER(LevelOutExtra), _FP]
         L.refnerf_activations_format.argtypes = [C.POINTER(LevelCfg)]
         L.refnerf_level_image.argtypes = [C.POINTER(LevelCfg)]
         L.refnerf_level_image.restype = C.c_int
@@ -165,6 +175,8 @@ def lib():
         L.refnerf_activation_workspace_bytes.argtypes = [C.c_int32, C.c_int32]
         L.refnerf_level_forward_train.argtypes = [_FP, C.POINTER(LevelCfg), C.POINTER(RaysStruct), C.c_int32,
                                                   _FP, _FP, C.POINTER(LevelOut), _FP, C.c_size_t, _FP]
+        L.refnerf_level_forward_train_ex.argtypes = [_FP, C.POINTER(LevelCfg), C.POINTER(RaysStruct), C.c_int32,
+                                                     _FP, _FP, C.POINTER(LevelOut), C.POINTER(LevelOutExtra), _FP, C.c_size_t, _FP]
         L.refnerf_backward_workspace_bytes.restype = C.c_size_t
         L.refnerf_backward_workspace_bytes_basis.restype = C.c_size_t
         L.refnerf_backward_workspace_bytes_basis.argtypes = [C.c_int32, C.c_int32, C.c_int32]
@@ -300,13 +312,20 @@ def pack_weights(params: torch.Tensor, packed: torch.Tensor = None, precision=PR
     return packed
 
 
-def level_forward(packed, cfg: LevelCfg, rays: dict, sdist_in, weights_in, history=True, save_activations=False):
+def level_forward(packed, cfg: LevelCfg, rays: dict, sdist_in=None, weights_in=None, history=True, save_activations=False,
+                  percentiles_soa=False):
     """One fused level.  rays: dict of device tensors (origins, directions,
     viewdirs [R,3]; radii, near, far [R] or [R,1]).  Returns dict of tensors.
+    sdist_in = weights_in = None (with cfg.n_in == 1): the model's initial step function, knots cfg.s_near / cfg.s_far and
+    weight 1 -- the library gets NULL pointers, reads nothing and resamples it in closed form (same bits as the tensors).
     save_activations (training forward): also keeps the layer inputs for
-    level_backward in res["activations"] (a byte tensor the backward consumes)."""
+    level_backward in res["activations"] (a byte tensor the backward consumes).
+    percentiles_soa: the float64 percentiles come as res["r_percentiles_soa"] [3, R] (each row one contiguous per-ray
+    output) instead of res["r_percentiles"] [R, 3].  res["r_rgb_fg"] [R, 3] = sum_i w_i rgb_i (r_rgb before the background)."""
     require_device()
-    dev = sdist_in.device
+    if (sdist_in is None) != (weights_in is None):
+        raise ValueError("level_forward: sdist_in and weights_in are given together, or both None (the initial step function)")
+    dev = rays["origins"].device
     R = rays["origins"].shape[0]
     N = cfg.n_samples
     rs = RaysStruct()
@@ -319,7 +338,7 @@ def level_forward(packed, cfg: LevelCfg, rays: dict, sdist_in, weights_in, histo
     res = {
         "sdist": torch.empty((R, N + 1), **f32), "bin_idx": torch.empty((R, N), dtype=torch.int32, device=dev),
         "weights": torch.empty((R, N), **f32),
-        "r_rgb": torch.empty((R, 3), **f32), "r_diffuse": torch.empty((R, 3), **f32),
+        "r_rgb": torch.empty((R, 3), **f32), "r_rgb_fg": torch.empty((R, 3), **f32), "r_diffuse": torch.empty((R, 3), **f32),
         "r_specular": torch.empty((R, 3), **f32), "r_distance": torch.empty((R,), **f32),
         "r_acc": torch.empty((R,), **f32),
     }
@@ -339,23 +358,27 @@ def level_forward(packed, cfg: LevelCfg, rays: dict, sdist_in, weights_in, histo
         res["r_tint"] = torch.empty((R, 3), **f32)
         res["r_roughness"] = torch.empty((R,), **f32)
         res["r_distance_mean"] = torch.empty((R,), **f32)
-        res["r_percentiles"] = torch.empty((R, 3), dtype=torch.float64, device=dev)
+        if percentiles_soa:
+            res["r_percentiles_soa"] = torch.empty((3, R), dtype=torch.float64, device=dev)
+        else:
+            res["r_percentiles"] = torch.empty((R, 3), dtype=torch.float64, device=dev)
         if cfg.training:
             res["r_normals"] = torch.empty((R, 3), **f32)
-    out = LevelOut()
+    out, extra = LevelOut(), LevelOutExtra()
     for k, t in res.items():
-        setattr(out, "d_" + k, t.data_ptr())
-    sd = sdist_in.to(torch.float32).contiguous()
-    w = weights_in.to(torch.float32).contiguous()
+        setattr(extra if "d_" + k in OUT_EXTRA_FIELDS else out, "d_" + k, t.data_ptr())
+    sd = None if sdist_in is None else sdist_in.to(torch.float32).contiguous()
+    w = None if weights_in is None else weights_in.to(torch.float32).contiguous()
     if save_activations:
         act = torch.empty(lib().refnerf_activation_workspace_bytes_basis(R, N, cfg.ipe_groups), dtype=torch.uint8, device=dev)
-        check(lib().refnerf_level_forward_train(ptr(packed), C.byref(cfg), C.byref(rs), R, ptr(sd), ptr(w), C.byref(out),
-                                                ptr(act), act.numel(), stream_ptr()))
+        check(lib().refnerf_level_forward_train_ex(ptr(packed), C.byref(cfg), C.byref(rs), R, ptr(sd), ptr(w), C.byref(out),
+                                                   C.byref(extra), ptr(act), act.numel(), stream_ptr()))
         res["activations"] = act
         # REFNERF_ACT_*: what this forward wrote (f32 rows | bf16 pair-rows | REFNERF_ACT_SQ), as the library says
         res["activations_format"] = int(lib().refnerf_activations_format(C.byref(cfg)))
     else:
-        check(lib().refnerf_level_forward(ptr(packed), C.byref(cfg), C.byref(rs), R, ptr(sd), ptr(w), C.byref(out), stream_ptr()))
+        check(lib().refnerf_level_forward_ex(ptr(packed), C.byref(cfg), C.byref(rs), R, ptr(sd), ptr(w), C.byref(out), C.byref(extra),
+                                             stream_ptr()))
     return res
 
 

@@ -695,9 +695,17 @@ BwdPlan bwd_plan(int R, int N, int groups = 0) {
 
 static int level_forward_impl(const void *d_packed, const refnerf_level_cfg *cfg, const refnerf_rays *rays,
                               int32_t R, const float *d_sdist_in, const float *d_weights_in,
-                              const refnerf_level_out *out, float *d_act, long long act_pitch, void *stream) {
-  if (!d_packed || !cfg || !rays || !out || !d_sdist_in || !d_weights_in)
+                              const refnerf_level_out *out, const refnerf_level_out_extra *extra, float *d_act, long long act_pitch,
+                              void *stream) {
+  if (!d_packed || !cfg || !rays || !out)
     return fail(REFNERF_EINVAL, "refnerf_level_forward: null pointer%s");
+  /* d_sdist_in = d_weights_in = NULL: the model's initial step function [s_near, s_far], weight 1 (closed form in the resampler) */
+  if (!d_sdist_in != !d_weights_in)
+    return fail(REFNERF_EINVAL, "refnerf_level_forward: d_sdist_in and d_weights_in are given together, or both NULL (the initial step function)%s");
+  if (!d_sdist_in && cfg->n_in != 1)
+    return fail(REFNERF_EINVAL, "refnerf_level_forward: a NULL step function is the initial one, n_in must be 1%s");
+  if (!d_sdist_in && !(cfg->s_far > cfg->s_near))
+    return fail(REFNERF_EINVAL, "refnerf_level_forward: a NULL step function needs s_near < s_far%s");
   if (R <= 0) return fail(REFNERF_EINVAL, "refnerf_level_forward: R must be positive%s");
   /* stepfun.py:234-235 */
   if (cfg->n_samples <= 1) return fail(REFNERF_EINVAL, "num_samples must be > 1%s");
@@ -735,7 +743,7 @@ static int level_forward_impl(const void *d_packed, const refnerf_level_cfg *cfg
                                 "the bottleneck rows in the activation buffer (d_packed: the REFNERF_IMAGE_F16X2_TRAIN image)%s");
   if (cfg->wgrad_mode == REFNERF_WGRAD_F16 && !train_sq)
     return fail(REFNERF_EUNSUPPORTED, "wgrad_mode = REFNERF_WGRAD_F16 belongs to training levels in REFNERF_PREC_F16X2 on the built-in IPE basis%s");
-  if (train_sq) return rnsq::forward(d_packed, cfg, rays, R, d_sdist_in, d_weights_in, out, d_act, (hipStream_t)stream);
+  if (train_sq) return rnsq::forward(d_packed, cfg, rays, R, d_sdist_in, d_weights_in, out, extra, d_act, (hipStream_t)stream);
   const bool split = cfg->precision == REFNERF_PREC_F16X2 && !gb_split;
   const bool bf = (cfg->precision == REFNERF_PREC_BF16 && !train_bf) || cfg->precision == REFNERF_PREC_F16 || split;     /* the LDS-ring 16-bit eval kernels */
   int rpw = rays_per_wg(N, bf ? rn::BT : rn::T_TILE);
@@ -790,6 +798,7 @@ static int level_forward_impl(const void *d_packed, const refnerf_level_cfg *cfg
   a.sdist_in = d_sdist_in;
   a.weights_in = d_weights_in;
   a.out = *out;
+  if (extra) a.xout = *extra;
   a.prof = nullptr;
   a.g_means = nullptr; a.g_covs = nullptr; a.cov_full = 0;
   a.act = d_act; a.act_pitch = act_pitch;
@@ -830,6 +839,10 @@ static int level_forward_impl(const void *d_packed, const refnerf_level_cfg *cfg
       fprintf(stderr, "[prof] wave %d:", w);
       for (int sl = 1; sl <= 18; ++sl) fprintf(stderr, " %lld", hbuf[w * 32 + sl] ? hbuf[w * 32 + sl] - hbuf[w * 32] : -1LL);
       fprintf(stderr, "  | dma-wait %lld barrier-wait %lld", hbuf[w * 32 + 20], hbuf[w * 32 + 21]);
+#ifdef REFNERF_PROF_WAITS
+      fprintf(stderr, " | P0 split");   /* stamps inside the resample phase (RN_STAMP_P0) */
+      for (int sl = 24; sl <= 28; ++sl) fprintf(stderr, " %lld", hbuf[w * 32 + sl] ? hbuf[w * 32 + sl] - hbuf[w * 32] : -1LL);
+#endif
       if (hbuf[w * 32 + 23] > hbuf[w * 32 + 22])   /* -DREFNERF_PROF_WAITS builds: shader clock from the 100 MHz counter */
         fprintf(stderr, " | clock %.0f MHz", 100.0 * (double)(hbuf[w * 32 + 15] - hbuf[w * 32]) / (double)(hbuf[w * 32 + 23] - hbuf[w * 32 + 22]));
       fprintf(stderr, "\n");
@@ -841,12 +854,19 @@ static int level_forward_impl(const void *d_packed, const refnerf_level_cfg *cfg
 int refnerf_level_forward(const void *d_packed, const refnerf_level_cfg *cfg, const refnerf_rays *rays,
                           int32_t R, const float *d_sdist_in, const float *d_weights_in,
                           const refnerf_level_out *out, void *stream) {
-  return level_forward_impl(d_packed, cfg, rays, R, d_sdist_in, d_weights_in, out, nullptr, 0, stream);
+  return level_forward_impl(d_packed, cfg, rays, R, d_sdist_in, d_weights_in, out, nullptr, nullptr, 0, stream);
 }
 
-int refnerf_level_forward_train(const void *d_packed, const refnerf_level_cfg *cfg, const refnerf_rays *rays,
+int refnerf_level_forward_ex(const void *d_packed, const refnerf_level_cfg *cfg, const refnerf_rays *rays,
+                             int32_t R, const float *d_sdist_in, const float *d_weights_in,
+                             const refnerf_level_out *out, const refnerf_level_out_extra *extra, void *stream) {
+  return level_forward_impl(d_packed, cfg, rays, R, d_sdist_in, d_weights_in, out, extra, nullptr, 0, stream);
+}
+
+int refnerf_level_forward_train_ex(const void *d_packed, const refnerf_level_cfg *cfg, const refnerf_rays *rays,
                                 int32_t R, const float *d_sdist_in, const float *d_weights_in,
-                                const refnerf_level_out *out, void *d_activations, size_t activations_bytes,
+                                const refnerf_level_out *out, const refnerf_level_out_extra *extra, void *d_activations,
+                                   size_t activations_bytes,
                                 void *stream) {
   if (!cfg || !d_activations) return fail(REFNERF_EINVAL, "refnerf_level_forward_train: null pointer%s");
   if (!cfg->training) return fail(REFNERF_EINVAL, "refnerf_level_forward_train: cfg->training must be 1%s");
@@ -854,7 +874,14 @@ int refnerf_level_forward_train(const void *d_packed, const refnerf_level_cfg *c
   const BwdPlan plan = bwd_plan(R, cfg->n_samples, cfg->ipe_groups);
   if (activations_bytes < plan.act_bytes)
     return fail(REFNERF_EINVAL, "refnerf_level_forward_train: activation buffer too small (see refnerf_activation_workspace_bytes)%s");
-  return level_forward_impl(d_packed, cfg, rays, R, d_sdist_in, d_weights_in, out, (float *)d_activations, plan.pitch, stream);
+  return level_forward_impl(d_packed, cfg, rays, R, d_sdist_in, d_weights_in, out, extra, (float *)d_activations, plan.pitch, stream);
+}
+
+int refnerf_level_forward_train(const void *d_packed, const refnerf_level_cfg *cfg, const refnerf_rays *rays,
+                                int32_t R, const float *d_sdist_in, const float *d_weights_in,
+                                const refnerf_level_out *out, void *d_activations, size_t activations_bytes,
+                                void *stream) {
+  return refnerf_level_forward_train_ex(d_packed, cfg, rays, R, d_sdist_in, d_weights_in, out, nullptr, d_activations, activations_bytes, stream);
 }
 
 /* both ray-generation entries; dist == NULL: the pinhole kernel */

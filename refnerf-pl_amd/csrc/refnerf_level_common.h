@@ -50,6 +50,7 @@ struct LevelArgs {
   const float *sdist_in;
   const float *weights_in;
   refnerf_level_out out;
+  refnerf_level_out_extra xout = {nullptr, nullptr};   /* the _ex entries; NULL everywhere else */
   long long *prof;   /* debug: per-phase cycle stamps of workgroup 0 (REFNERF_PROF=1), else NULL */
   /* MLP stage entry (refnerf_mlp_forward): caller-supplied Gaussians instead of resample + cast */
   const float *g_means;   /* [R,N,3] */
@@ -63,6 +64,14 @@ struct LevelArgs {
 };
 
 #define RN_STAMP(A, slot) do { asm volatile("; RNMARK " #slot); if ((A).prof && blockIdx.x == (gridDim.x >> 1) && (threadIdx.x & 63) == 0) (A).prof[(threadIdx.x >> 6) * 32 + (slot)] = (long long)__builtin_readcyclecounter(); } while (0)
+
+/* -DREFNERF_PROF_WAITS builds only: stamps INSIDE the resample phase (slots 24..28: knots loaded, logits formed, CDF built,
+ * CDF inverted + edges, ray geometry parked; slot 1 closes the phase).  The shipped kernels carry none of them. */
+#ifdef REFNERF_PROF_WAITS
+#define RN_STAMP_P0(A, slot) RN_STAMP(A, slot)
+#else
+#define RN_STAMP_P0(A, slot) do { } while (0)
+#endif
 
 /* Index into an LDS tile of 128-float rows for a compile-time row: rows whose byte offset passes the 64 KB immediate
  * range of the ds instructions go through `hi` = a LAUNDERED 128 * 128 + column (tile_hi()), so that one register
@@ -128,6 +137,31 @@ __device__ __forceinline__ double wave_scan_incl(double v, int lane) {
   return v;
 }
 
+/* math.sorted_interp at one centre (math.py:96-111): u in CDF bin [xp0, xp1] -> its place between the knots fp0, fp1.  The
+ * one expression a sample centre comes out of; on the initial step function (xp = {0, 1}) it is fp0 + clip01(u) (fp1 - fp0). */
+__device__ __forceinline__ float cdf_interp(float u, float xp0, float xp1, float fp0, float fp1) {
+  float q = (u - xp0) / (xp1 - xp0);
+  if (q != q) q = 0.0f;                       /* nan_to_num(., 0) */
+  float off = clip01(q);                      /* +-inf clip like +-FLT_MAX */
+  return fp0 + off * (fp1 - fp0);
+}
+
+/* stepfun.py:246-256: the N centres c (LDS, written by this wave) -> the N + 1 interval edges sd, clamped to [smin, smax] */
+__device__ __forceinline__ void centres_to_sdist(const float *c, int N, float smin, float smax, float *sd, int lane) {
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  #pragma clang loop unroll(disable)
+  for (int k = lane; k <= N; k += 64) {
+    float v;
+    if (k == 0) v = fmaxf(smin, 2.0f * c[0] - (c[1] + c[0]) / 2.0f);
+    else if (k == N) v = fminf(smax, 2.0f * c[N - 1] - (c[N - 1] + c[N - 2]) / 2.0f);
+    else v = (c[k] + c[k - 1]) / 2.0f;
+    sd[k] = v;
+  }
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
+
 /* stepfun.sample_intervals (stepfun.py:209-258) for one ray, executed by one
  * wave.  t_in[M+1], logits in LDS scratch `lg[M]`; writes sdist[N+1] to `sd`
  * (LDS) and optional bin indices.  Scratch: e[M] (aliases lg), cw[M+1], c[N].
@@ -135,8 +169,7 @@ __device__ __forceinline__ double wave_scan_incl(double v, int lane) {
  * CDF is bit-identical to theirs; the chain runs wave-uniformly on values fetched with v_readlane (no LDS round trip per
  * term), every lane ends up with the same sums. */
 template <bool EXACT = true>
-__device__ __forceinline__ void sample_intervals_wave(const float *t_in, float *lg, float *cw, float *c, int M, int N,
-                                      float smin, float smax, float *sd, int32_t *bin_idx_g, int lane) {
+__device__ __forceinline__ void build_cdf_wave(float *lg, float *cw, int M, int lane) {
   /* softmax: max is order-independent */
   float mx = -INFINITY;
   #pragma clang loop unroll(disable)
@@ -196,7 +229,12 @@ __device__ __forceinline__ void sample_intervals_wave(const float *t_in, float *
   }
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
   __builtin_amdgcn_wave_barrier();
-  /* inverse CDF at the deterministic centres (math.py:88-111) */
+}
+
+/* ... second half: the inverse CDF at the deterministic centres (math.py:88-111) on the knots t_in[M+1] and the CDF cw[M+1]
+ * (LDS, visible to the wave), then the centre -> edge pass */
+__device__ __forceinline__ void invert_cdf_wave(const float *t_in, const float *cw, float *c, int M, int N, float smin, float smax,
+                                                float *sd, int32_t *bin_idx_g, int lane) {
   #pragma clang loop unroll(disable)
   for (int k = lane; k < N; k += 64) {
     float u = linspace_u(k, N);
@@ -207,25 +245,17 @@ __device__ __forceinline__ void sample_intervals_wave(const float *t_in, float *
       int mid = (lo + hi) >> 1;
       if (u >= cw[mid]) lo = mid; else hi = mid;
     }
-    float xp0 = cw[lo], xp1 = cw[lo + 1], fp0 = t_in[lo], fp1 = t_in[lo + 1];
-    float q = (u - xp0) / (xp1 - xp0);
-    if (q != q) q = 0.0f;                       /* nan_to_num(., 0) */
-    float off = clip01(q);                      /* +-inf clip like +-FLT_MAX */
-    c[k] = fp0 + off * (fp1 - fp0);
+    c[k] = cdf_interp(u, cw[lo], cw[lo + 1], t_in[lo], t_in[lo + 1]);
     if (bin_idx_g) bin_idx_g[k] = lo;
   }
-  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  #pragma clang loop unroll(disable)
-  for (int k = lane; k <= N; k += 64) {
-    float v;
-    if (k == 0) v = fmaxf(smin, 2.0f * c[0] - (c[1] + c[0]) / 2.0f);
-    else if (k == N) v = fminf(smax, 2.0f * c[N - 1] - (c[N - 1] + c[N - 2]) / 2.0f);
-    else v = (c[k] + c[k - 1]) / 2.0f;
-    sd[k] = v;
-  }
-  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-  __builtin_amdgcn_wave_barrier();
+  centres_to_sdist(c, N, smin, smax, sd, lane);
+}
+
+template <bool EXACT = true>
+__device__ __forceinline__ void sample_intervals_wave(const float *t_in, float *lg, float *cw, float *c, int M, int N,
+                                      float smin, float smax, float *sd, int32_t *bin_idx_g, int lane) {
+  build_cdf_wave<EXACT>(lg, cw, M, lane);
+  invert_cdf_wave(t_in, cw, c, M, N, smin, smax, sd, bin_idx_g, lane);
 }
 
 /* this lane's index within the wave, formed HERE (round 6): a lane constant derived from it lives from this point on, not from
@@ -261,19 +291,37 @@ __device__ __forceinline__ void resample_phase(const LevelArgs &A, float *scratc
   for (int rl = wave; rl < rpw; rl += NW) {
     int ray = ray0 + rl;
     if (ray >= A.R) break;
-    const float *tg = A.sdist_in + (size_t)ray * (M + 1);
-    const float *wg = A.weights_in + (size_t)ray * M;
-    #pragma clang loop unroll(disable)
-    for (int i = lane; i <= M; i += 64) t_in[i] = tg[i];
-    wave_sync();
-    /* models.py:200-203 */
-    #pragma clang loop unroll(disable)
-    for (int i = lane; i < M; i += 64)
-      lg[i] = (t_in[i + 1] > t_in[i]) ? cfg.anneal * rn_det_logf(wg[i] + cfg.resample_padding) : -INFINITY;   /* shared with the oracle: bit-identical logits */
-    wave_sync();
     float *sd = TD + rl * (N + 1);
-    sample_intervals_wave<EXACT>(t_in, lg, cw, c, M, N, cfg.s_near, cfg.s_far, sd,
-                          A.out.d_bin_idx ? A.out.d_bin_idx + (size_t)ray * N : nullptr, lane);
+    int32_t *bin_g = A.out.d_bin_idx ? A.out.d_bin_idx + (size_t)ray * N : nullptr;
+    if (A.sdist_in == nullptr) {
+      /* The step function every Model.__call__ starts from (models.py:153-157; the host checked M == 1, s_near < s_far): ONE
+       * interval [s_near, s_far] of weight 1.  Its only logit softmaxes to exactly 1 whatever anneal and padding are, so the
+       * CDF is {0, 1}: the knots and the CDF are WRITTEN here (every lane the same four values: no divergent branch, whose
+       * saved exec mask would be one more spilled scalar pair in the 16-bit kernels) and the inversion below runs on them --
+       * bin 0 for every centre, (u - 0) / (1 - 0) = u, c_k = s_near + clip01(u_k) (s_far - s_near) out of the same
+       * cdf_interp as any other step function.  Nothing is read from HBM, no log / exp, no sequential chains.  The branch is
+       * on a kernel argument: uniform over the launch. */
+      t_in[0] = cfg.s_near; t_in[1] = cfg.s_far;
+      cw[0] = 0.0f; cw[1] = 1.0f;
+      wave_sync();
+    } else {
+      const float *tg = A.sdist_in + (size_t)ray * (M + 1);
+      const float *wg = A.weights_in + (size_t)ray * M;
+      #pragma clang loop unroll(disable)
+      for (int i = lane; i <= M; i += 64) t_in[i] = tg[i];
+      wave_sync();
+      RN_STAMP_P0(A, 24);
+      /* models.py:200-203 */
+      #pragma clang loop unroll(disable)
+      for (int i = lane; i < M; i += 64)
+        lg[i] = (t_in[i + 1] > t_in[i]) ? cfg.anneal * rn_det_logf(wg[i] + cfg.resample_padding) : -INFINITY;   /* shared with the oracle: bit-identical logits */
+      wave_sync();
+      RN_STAMP_P0(A, 25);
+      build_cdf_wave<EXACT>(lg, cw, M, lane);
+    }
+    RN_STAMP_P0(A, 26);
+    invert_cdf_wave(t_in, cw, c, M, N, cfg.s_near, cfg.s_far, sd, bin_g, lane);
+    RN_STAMP_P0(A, 27);
     float nearv = A.rays.d_near[ray], farv = A.rays.d_far[ray];
     /* bf16 kernel only (the fp32 kernels keep their proven code path): the ray's geometry goes to LDS once --
      * NRM[rl] = |d| for the compositing phase and, behind the rpw norms, 12 floats per ray
@@ -290,6 +338,7 @@ __device__ __forceinline__ void resample_phase(const LevelArgs &A, float *scratc
         if (lane == 0) NRM[rl] = sqrtf((dx * dx + dy * dy) + dz * dz);
       }
     }
+    RN_STAMP_P0(A, 28);
     #pragma clang loop unroll(disable)
     for (int k = lane; k <= N; k += 64) {
       float s = sd[k];
@@ -483,6 +532,23 @@ __device__ __forceinline__ void history_flush(const LevelArgs &A, const float *P
   if (NP > PS_NORMALS && A.cfg.training) vec3(A.out.d_normals, PS_NORMALS);
 }
 
+/* An output pointer of the launch as the phase that stores through it sees it: LAUNDERED, so that its NULL test is formed
+ * there.  Left to itself the compiler evaluates the tests of the output pointers at the kernel's entry and carries the results
+ * through every trunk in spilled scalar registers.  Their holders are vector registers: level_fwd_f16x2 sits at 256 VGPR with
+ * four of them holding spilled scalars (240 before these two pointers), and a fifth holder is 8 B/lane of scratch (EXPERIMENTS section 17).  Used for the
+ * two pointers of refnerf_level_out_extra, so that they add no more than their own four slots. */
+template <typename T>
+__device__ __forceinline__ T *late_ptr(T *p) {
+  asm volatile("" : "+s"(p));
+  return p;
+}
+
+/* percentile p of a ray: into the [3, R] buffer when the caller gave one (row p = one contiguous per-ray output), else [R, 3] */
+__device__ __forceinline__ void pct_store(double *soa, double *aos, int R, int ray, int p, double v) {
+  if (soa) soa[(size_t)p * R + ray] = v;
+  else aos[(size_t)ray * 3 + p] = v;
+}
+
 /* P7: alpha weights + compositing, one wave per ray (render.py:132-149, 152-254). */
 /* rays [rl_begin, rl_end) of the workgroup (default: all of them); PSM: ring of per-sample records (see ps_row), in which
  * case the cross-lane sums go through shuffles instead of the LDS scratch `wscr` (it is not free while passes are running) */
@@ -596,6 +662,7 @@ __device__ __forceinline__ void composite_phase(const LevelArgs &A, const float 
     }
     if (lane == 0) {
       st3(A.out.d_r_rgb, ray, rgb[0], rgb[1], rgb[2]);
+      st3(late_ptr(A.xout.d_r_rgb_fg), ray, s_rgb[0], s_rgb[1], s_rgb[2]);     /* before the background term: models.py:310 */
       st3(A.out.d_r_diffuse, ray, dif[0], dif[1], dif[2]);
       st3(A.out.d_r_specular, ray, spc[0], spc[1], spc[2]);
       if (A.out.d_r_distance) A.out.d_r_distance[ray] = s_dist;
@@ -623,7 +690,8 @@ __device__ __forceinline__ void composite_phase(const LevelArgs &A, const float 
       }
     }
     /* percentiles (stepfun.py:294-307, math.py:114-142) in float64 */
-    if (cfg.compute_extras && A.out.d_r_percentiles) {
+    double *const pct_soa = late_ptr(A.xout.d_r_percentiles_soa), *const pct_aos = A.out.d_r_percentiles;
+    if (cfg.compute_extras && (pct_aos || pct_soa)) {
       /* knots xp[j], j = 0..N+1: xp[0]=0, xp[j]=min(1,float(cumsum w[0..j-1])), xp[N+1]=1.
        * fp[j] = td[j] (j<=N), fp[N+1]=far. */
       float *xp = XP + rl * (N + 1);
@@ -664,7 +732,7 @@ __device__ __forceinline__ void composite_phase(const LevelArgs &A, const float 
           double f0 = (double)td[idx], f1 = (idx + 1 == nk - 1) ? (double)farv : (double)td[idx + 1];
           double m = (f1 - f0) / (x1 - x0);
           double b = f0 - m * x0;
-          A.out.d_r_percentiles[(size_t)ray * 3 + lane] = m * x + b;
+          pct_store(pct_soa, pct_aos, A.R, ray, lane, m * x + b);
         }
       } else {
         #pragma clang loop unroll(disable)
@@ -686,7 +754,7 @@ __device__ __forceinline__ void composite_phase(const LevelArgs &A, const float 
             double f0 = (double)td[idx], f1 = (idx + 1 == nk - 1) ? (double)farv : (double)td[idx + 1];
             double m = (f1 - f0) / (x1 - x0);
             double b = f0 - m * x0;
-            A.out.d_r_percentiles[(size_t)ray * 3 + p] = m * x + b;
+            pct_store(pct_soa, pct_aos, A.R, ray, p, m * x + b);
           }
         }
       }

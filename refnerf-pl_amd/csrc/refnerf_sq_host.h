@@ -23,7 +23,7 @@ size_t image_bytes();
 int pack(const float *d_params, void *d_packed, hipStream_t st);
 /* the training forward of one level (REFNERF_PREC_F16X2, built-in basis); d_act: REFNERF_ACT_SQ */
 int forward(const void *d_packed, const refnerf_level_cfg *cfg, const refnerf_rays *rays, int R, const float *d_sdist_in,
-            const float *d_weights_in, const refnerf_level_out *out, float *d_act, hipStream_t st);
+            const float *d_weights_in, const refnerf_level_out *out, const refnerf_level_out_extra *extra, float *d_act, hipStream_t st);
 /* the per-sample backward (the seeds are already in `d_seeds`): writes DELTA + the factor units */
 int backward_chain(const void *d_packed, const refnerf_level_cfg *cfg, const refnerf_rays *rays, int R, const float *d_sdist,
                    const refnerf_level_grads *grads, const float *d_act, float *d_delta, const float *d_seeds, long long pitch,

@@ -232,7 +232,7 @@ static size_t fwd_lds_bytes(int rays, int N) {
 }
 
 int forward(const void *d_packed, const refnerf_level_cfg *cfg, const refnerf_rays *rays, int R, const float *d_sdist_in,
-            const float *d_weights_in, const refnerf_level_out *out, float *d_act, hipStream_t st) {
+            const float *d_weights_in, const refnerf_level_out *out, const refnerf_level_out_extra *extra, float *d_act, hipStream_t st) {
   const int N = cfg->n_samples;
   int rpw = rays_per_wg_sq(N);
   /* the per-ray phases (resample, compositing) occupy one wave per ray: as many rays per workgroup as the LDS holds */
@@ -259,6 +259,7 @@ int forward(const void *d_packed, const refnerf_level_cfg *cfg, const refnerf_ra
   a.sdist_in = d_sdist_in;
   a.weights_in = d_weights_in;
   a.out = *out;
+  if (extra) a.xout = *extra;
   a.prof = nullptr;
   a.g_means = nullptr; a.g_covs = nullptr; a.cov_full = 0;
   a.act = d_act; a.act_pitch = 0;

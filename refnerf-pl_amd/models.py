@@ -506,7 +506,7 @@ class _LevelFunction(torch.autograd.Function):
             packed = mlp.packed_weights(image, force=True)
             if reuse is not None:
                 reuse[(id(mlp), image)] = packed
-        res = _hip.level_forward(packed, cfg, rays, sdist_in, weights_in, history=True, save_activations=True)
+        res = _hip.level_forward(packed, cfg, rays, sdist_in, weights_in, history=True, save_activations=True, percentiles_soa=True)
         ctx.mlp, ctx.cfg, ctx.rays, ctx.packed = mlp, cfg, rays, packed
         ctx.packed_key = mlp._packed_key
         ctx.set_materialize_grads(False)           # outputs without an upstream gradient arrive as None, not as zero tensors
@@ -652,8 +652,8 @@ class Model(nn.Module):
 
     def _specular_density(self, mlp: MLP, cfg, r, sdist_in, weights_in):
         """ray_results['specular_density'] of one level (MLP.packed_specular_weights): the level's inference kernel in
-        Config.hip_precision on the image whose density head is the specular-density head, same incoming step function -> same
-        samples; its `density` output.  Detached: no loss of the reference reads it (the head's gradient is None there too)."""
+        Config.hip_precision on the image whose density head is the specular-density head, same incoming step function (None at
+        level 0: the initial one) -> same samples; its `density` output.  Detached: no loss of the reference reads it (the head's gradient is None there too)."""
         import ctypes
         cfg2 = type(cfg)()
         ctypes.memmove(ctypes.byref(cfg2), ctypes.byref(cfg), ctypes.sizeof(cfg))
@@ -661,7 +661,8 @@ class Model(nn.Module):
         cfg2.precision = _PREC[getattr(self.config, "hip_precision", "f32")]
         image = _hip.level_image(cfg2.precision, False, mlp.ipe_groups)
         with torch.no_grad():
-            res = _hip.level_forward(mlp.packed_specular_weights(image), cfg2, r, sdist_in.detach(), weights_in.detach(), history=("density",))
+            res = _hip.level_forward(mlp.packed_specular_weights(image), cfg2, r, None if sdist_in is None else sdist_in.detach(),
+                                     None if weights_in is None else weights_in.detach(), history=("density",))
         return res["density"]
 
     def _level_cfg(self, mlp: MLP, n_samples, n_in, train_frac, compute_extras):
@@ -729,10 +730,9 @@ class Model(nn.Module):
              "viewdirs": flat(rays.viewdirs, 3), "radii": flat(rays.radii, 1).reshape(-1),
              "near": flat(rays.near, 1).reshape(-1), "far": flat(rays.far, 1).reshape(-1)}
         R = r["origins"].shape[0]
-        # models.py:153-157
-        sdist = torch.cat([torch.full((R, 1), float(self.init_s_near), device=dev),
-                           torch.full((R, 1), float(self.init_s_far), device=dev)], dim=-1)
-        weights = torch.ones((R, 1), device=dev)
+        # models.py:153-157: the initial step function [init_s_near, init_s_far], weight 1, is not materialised -- level 0 gets
+        # None and the kernel resamples it in closed form from cfg.s_near / s_far (refnerf_level_forward)
+        sdist = weights = None
         renderings, ray_history = [], []
         # diagnostic (not part of the reference's return value): the CDF bin index of every sample, per level --
         # north_star's "sample indices"; bench.py and the parity tests compare them between arithmetic modes
@@ -765,7 +765,7 @@ class Model(nn.Module):
                                                                     domain=(self.init_s_near, self.init_s_far), renormalize=True)
                         sdist, weights = sdist[..., 1:-1].contiguous(), weights[..., 1:-1].contiguous()
             mlp = self.prop_mlp if is_prop else self.nerf_mlp
-            cfg = self._level_cfg(mlp, num_samples, weights.shape[-1], train_frac, compute_extras)
+            cfg = self._level_cfg(mlp, num_samples, 1 if weights is None else weights.shape[-1], train_frac, compute_extras)
             sd_in, w_in = sdist, weights                     # this level's incoming step function (the specular-density launch re-reads it)
             if self.training and torch.is_grad_enabled():
                 # one autograd node per level; sdist / resampling inputs are detached (models.py:205-216)
@@ -793,7 +793,8 @@ class Model(nn.Module):
                     mlp.release_flat_parameter()            # flat mode was switched off: no stale .grad on the blob
                 holder = {"bwd_precision": _PREC[bwd_prec], "flat_mode": flat_mode, "call_images": call_images}
                 diff_inputs = (mlp.flat_parameter(),) if flat_mode else tuple(mlp.ordered_parameters())
-                outs = _LevelFunction.apply(mlp, cfg, r, holder, sdist.detach(), weights.detach(), *diff_inputs)
+                outs = _LevelFunction.apply(mlp, cfg, r, holder, None if sdist is None else sdist.detach(),
+                                            None if weights is None else weights.detach(), *diff_inputs)
                 res = dict(zip(holder["keys"], outs))
             else:
                 lean = _LEAN.depth > 0 and not self.training
@@ -803,7 +804,8 @@ class Model(nn.Module):
                 #  and bottleneck rows in the activation buffer, so it gets one and drops it)
                 scratch_act = image == _hip.IMAGE_F16X2_TRAIN
                 res = _hip.level_forward(mlp.packed_weights(image), cfg, r, sdist, weights,
-                                         history=(("rgb",) if compute_extras else ()) if lean else True, save_activations=scratch_act)
+                                         history=(("rgb",) if compute_extras else ()) if lean else True, save_activations=scratch_act,
+                                         percentiles_soa=True)
                 if scratch_act:
                     res.pop("activations", None)
                     res.pop("activations_format", None)
@@ -826,10 +828,10 @@ class Model(nn.Module):
                 if mlp.enable_pred_roughness:
                     rendering["roughness"] = rs(res["r_roughness"], 1)
                 rendering["distance_mean"] = rs(res["r_distance_mean"])
-                pct = res["r_percentiles"]
-                rendering["distance_percentile_5"] = rs(pct[:, 0].contiguous())
-                rendering["distance_median"] = rs(pct[:, 1].contiguous())
-                rendering["distance_percentile_95"] = rs(pct[:, 2].contiguous())
+                pct = res["r_percentiles_soa"]                                   # [3, R]: each row a contiguous view, no copy
+                rendering["distance_percentile_5"] = rs(pct[0])
+                rendering["distance_median"] = rs(pct[1])
+                rendering["distance_percentile_95"] = rs(pct[2])
                 n = self.config.vis_num_rays                                     # models.py:290-301
                 rendering["ray_sdist"] = sdist[:n, :]
                 rendering["ray_weights"] = weights[:n, :]
@@ -857,9 +859,9 @@ class Model(nn.Module):
             ray_history.append(ray_results)
 
         if compute_extras:                                                       # models.py:308-319
-            ws = [x['ray_weights'] for x in renderings]
             rgbs = [x['ray_rgbs'] for x in renderings]
-            final_rgb = torch.sum(rgbs[-1] * ws[-1][..., None], dim=-2)
+            # sum_i w_i rgb_i of the last level: the compositing phase has it in registers (refnerf_level_out_extra.d_r_rgb_fg)
+            final_rgb = res["r_rgb_fg"][:self.config.vis_num_rays]
             for i in range(len(rgbs) - 1):
                 renderings[i]['ray_rgbs'] = torch.broadcast_to(final_rgb[:, None, :], rgbs[i].shape)
         return renderings, ray_history
