@@ -406,6 +406,41 @@ int refnerf_pixels_to_rays_distorted(const int32_t *d_pix_x, const int32_t *d_pi
                                      float *d_radii, float *d_imageplane,
                                      const refnerf_lens_distortion *distortion, void *stream);
 
+/* A whole frame's rays from (width, height, camera, pose) in one launch:
+ * Dataset.generate_ray_batch (internal/datasets.py:487-498) for the flat,
+ * row-major pixel range [first, first + count) of a width x height image, so a
+ * rank of a sharded render produces only its own rays.  No pixel-index input;
+ * all nine utils.Rays fields out (64 B/ray). */
+#define REFNERF_PROJ_PINHOLE 0
+#define REFNERF_PROJ_SPHERICAL 1
+typedef struct refnerf_image_rays_out {
+  float *d_origins, *d_directions, *d_viewdirs; /* [count,3] */
+  float *d_radii;                               /* [count] */
+  float *d_imageplane;                          /* [count,2]; may be NULL, as may every pointer below */
+  float *d_lossmult, *d_near, *d_far;           /* [count]: 1, near, far */
+  int32_t *d_cam_idx;                           /* [count]: frame (pinhole), 0 (spherical) */
+} refnerf_image_rays_out;
+
+/* The pose is d_camtoworlds + 12 * frame of the [n_frames,3,4] path.
+ * REFNERF_PROJ_PINHOLE: the arithmetic of refnerf_pixels_to_rays (or, with
+ * `distortion`, of refnerf_pixels_to_rays_distorted) on pixel (x, y) =
+ * (index % width, index / width): origins, directions, viewdirs, radii and
+ * imageplane are bit-identical to those entries' on the same pixels.
+ * REFNERF_PROJ_SPHERICAL: camera_utils.cast_spherical_rays (:700-746), an
+ * equirectangular panorama; d_pixtocam is unused (may be NULL), viewdirs =
+ * directions, imageplane = 0; directions and radii are computed in double from
+ * the float32 pose and rounded at the store.
+ * REFNERF_EINVAL: an unknown projection, a NULL required pointer, a
+ * non-positive size, frame outside [0, n_frames), a range outside the image,
+ * NDC or distortion with the spherical projection, or a `distortion` that
+ * refnerf_pixels_to_rays_distorted refuses. */
+int refnerf_image_rays(int32_t projection, int32_t width, int32_t height,
+                       const float *d_pixtocam, const float *d_camtoworlds,
+                       int32_t n_frames, int32_t frame, const float *d_pixtocam_ndc,
+                       const refnerf_lens_distortion *distortion, float near, float far,
+                       int64_t first, int32_t count, const refnerf_image_rays_out *out,
+                       void *stream);
+
 /* Stage entry points (same device code as the fused kernel; used by the
  * parity tests and for drop-in use of the individual reference functions). */
 

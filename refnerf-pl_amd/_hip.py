@@ -79,6 +79,15 @@ class LensDistortion(C.Structure):
     _fields_ = [(n, C.c_double) for n in ("k1", "k2", "k3", "k4", "p1", "p2", "eps")] + [("max_iterations", C.c_int32)]
 
 
+PROJ_PINHOLE, PROJ_SPHERICAL = 0, 1   # REFNERF_PROJ_*
+
+
+class ImageRaysOut(C.Structure):
+    """refnerf_image_rays_out: the nine utils.Rays fields."""
+    _fields_ = [(n, _FP) for n in ("d_origins", "d_directions", "d_viewdirs", "d_radii", "d_imageplane", "d_lossmult", "d_near",
+                                   "d_far", "d_cam_idx")]
+
+
 class AdamCfg(C.Structure):
     """refnerf_adam_cfg: one Adam step's scalars, computed by the host in double."""
     _fields_ = [(n, C.c_double) for n in ("lr", "beta1", "beta2", "eps", "bias_correction1", "sqrt_bias_correction2",
@@ -189,6 +198,9 @@ def lib():
                                              _FP, _FP, _FP, _FP, _FP, _FP]
         L.refnerf_pixels_to_rays_distorted.argtypes = [_FP, _FP, _FP, C.c_int32, _FP, C.c_int32, _FP, C.c_int32,
                                                        _FP, _FP, _FP, _FP, _FP, C.POINTER(LensDistortion), _FP]
+        L.refnerf_image_rays.argtypes = [C.c_int32, C.c_int32, C.c_int32, _FP, _FP, C.c_int32, C.c_int32, _FP,
+                                         C.POINTER(LensDistortion), C.c_float, C.c_float, C.c_int64, C.c_int32,
+                                         C.POINTER(ImageRaysOut), _FP]
         L.refnerf_mlp_forward.argtypes = [_FP, C.POINTER(LevelCfg), _FP, _FP, C.c_int32, _FP, C.c_int32, C.c_int32,
                                           C.POINTER(LevelOut), _FP]
         L.refnerf_sample_intervals.argtypes = [_FP, _FP, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float,
@@ -404,6 +416,31 @@ def pixels_to_rays(pix_x, pix_y, pixtocams, camtoworlds, pixtocam_ndc=None, dist
     else:
         check(lib().refnerf_pixels_to_rays_distorted(*args, C.byref(distortion), stream_ptr()))
     return o, d, v, r, ip
+
+
+def image_rays(projection, width, height, pixtocam, camtoworlds, frame, near, far, pixtocam_ndc=None,
+               distortion: LensDistortion = None, first=0, count=None):
+    """refnerf_image_rays: the nine utils.Rays fields (a dict, RAY_FIELDS order, each [count, width of the field]) of the
+    flat pixel range [first, first + count) of frame `frame` of the device-resident path `camtoworlds` [F,3,4], in one
+    launch.  `pixtocam` [3,3] device tensor (None for PROJ_SPHERICAL)."""
+    require_device()
+    c2w = camtoworlds
+    assert c2w.dtype == torch.float32 and c2w.dim() == 3 and tuple(c2w.shape[1:]) == (3, 4), "camtoworlds: float32 [F,3,4]"
+    assert pixtocam is None or (pixtocam.dtype == torch.float32 and tuple(pixtocam.shape) == (3, 3)), "pixtocam: float32 [3,3]"
+    assert pixtocam_ndc is None or (pixtocam_ndc.dtype == torch.float32 and tuple(pixtocam_ndc.shape) == (3, 3))
+    width, height, first = int(width), int(height), int(first)
+    count = width * height - first if count is None else int(count)
+    if not 0 <= count < 2 ** 31:
+        raise ValueError(f"refnerf_image_rays: count {count} outside [0, 2^31)")
+    dev = c2w.device
+    out, res = ImageRaysOut(), {}
+    for name, w in zip(RAY_FIELDS, RAY_FIELD_WIDTHS):
+        res[name] = torch.empty((count, w), dtype=torch.int32 if name == "cam_idx" else torch.float32, device=dev)
+        setattr(out, "d_" + name, res[name].data_ptr())
+    check(lib().refnerf_image_rays(int(projection), width, height, ptr(pixtocam), ptr(c2w), c2w.shape[0], int(frame),
+                                   ptr(pixtocam_ndc), None if distortion is None else C.byref(distortion), float(near),
+                                   float(far), first, count, C.byref(out), stream_ptr()))
+    return res
 
 
 def mlp_forward(packed, cfg: LevelCfg, means, covs, viewdirs):

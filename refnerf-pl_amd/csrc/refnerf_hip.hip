@@ -935,6 +935,52 @@ int refnerf_pixels_to_rays_distorted(const int32_t *d_pix_x, const int32_t *d_pi
                              d_radii, d_imageplane, distortion, stream);
 }
 
+int refnerf_image_rays(int32_t projection, int32_t width, int32_t height, const float *d_pixtocam, const float *d_camtoworlds,
+                       int32_t n_frames, int32_t frame, const float *d_pixtocam_ndc, const refnerf_lens_distortion *distortion,
+                       float near, float far, int64_t first, int32_t count, const refnerf_image_rays_out *out, void *stream) {
+  if (projection != REFNERF_PROJ_PINHOLE && projection != REFNERF_PROJ_SPHERICAL)
+    return fail(REFNERF_EINVAL, "refnerf_image_rays: unknown projection%s");
+  const bool spherical = projection == REFNERF_PROJ_SPHERICAL;
+  if (width <= 0 || height <= 0 || n_frames <= 0 || count <= 0)
+    return fail(REFNERF_EINVAL, "refnerf_image_rays: width, height, n_frames and count must be positive%s");
+  if (frame < 0 || frame >= n_frames) return fail(REFNERF_EINVAL, "refnerf_image_rays: frame outside [0, n_frames)%s");
+  if (first < 0 || first + (int64_t)count > (int64_t)width * height)
+    return fail(REFNERF_EINVAL, "refnerf_image_rays: [first, first + count) outside the image%s");
+  if (!d_camtoworlds || !out || !out->d_origins || !out->d_directions || !out->d_viewdirs || !out->d_radii ||
+      (!spherical && !d_pixtocam))
+    return fail(REFNERF_EINVAL, "refnerf_image_rays: null pointer%s");
+  if (spherical && (d_pixtocam_ndc || distortion))
+    return fail(REFNERF_EINVAL, "refnerf_image_rays: the spherical projection takes neither NDC nor lens distortion%s");
+  if (distortion) {
+    const double c[7] = {distortion->k1, distortion->k2, distortion->k3, distortion->k4, distortion->p1, distortion->p2,
+                         distortion->eps};
+    for (double v : c)
+      if (!std::isfinite(v)) return fail(REFNERF_EINVAL, "refnerf_image_rays: non-finite distortion parameter%s");
+    if (distortion->max_iterations < 0 || distortion->max_iterations > REFNERF_MAX_UNDISTORT_ITERATIONS)
+      return fail(REFNERF_EINVAL, "refnerf_image_rays: max_iterations must be in [0, 64]%s");
+  }
+  rn::ImageRaysArgs a{};
+  a.width = width; a.height = height; a.first = first; a.count = count;
+  a.pixtocam = d_pixtocam; a.camtoworld = d_camtoworlds + (size_t)12 * frame; a.pixtocam_ndc = d_pixtocam_ndc;
+  a.near = near; a.far = far;
+  a.cam_idx = spherical ? 0 : frame;      /* cast_spherical_rays broadcasts 0 whatever the frame (camera_utils.py:743) */
+  a.origins = out->d_origins; a.directions = out->d_directions; a.viewdirs = out->d_viewdirs; a.radii = out->d_radii;
+  a.imageplane = out->d_imageplane; a.lossmult = out->d_lossmult; a.near_out = out->d_near; a.far_out = out->d_far;
+  a.cam_idx_out = out->d_cam_idx;
+  const dim3 grid((unsigned)(((int64_t)count + 255) / 256)), block(256);
+  if (spherical) {
+    hipLaunchKernelGGL((rn::image_rays_kernel<true, false>), grid, block, 0, (hipStream_t)stream, a);
+  } else if (distortion) {
+    a.dist = {distortion->k1, distortion->k2, distortion->k3, distortion->k4, distortion->p1, distortion->p2, distortion->eps,
+              distortion->max_iterations};
+    hipLaunchKernelGGL((rn::image_rays_kernel<false, true>), grid, block, 0, (hipStream_t)stream, a);
+  } else {
+    hipLaunchKernelGGL((rn::image_rays_kernel<false, false>), grid, block, 0, (hipStream_t)stream, a);
+  }
+  HIP_TRY(hipGetLastError());
+  return REFNERF_OK;
+}
+
 int refnerf_mlp_forward(const void *d_packed, const refnerf_level_cfg *cfg, const float *d_means, const float *d_covs,
                         int32_t cov_is_full, const float *d_viewdirs, int32_t R, int32_t N, const refnerf_level_out *out,
                         void *stream) {

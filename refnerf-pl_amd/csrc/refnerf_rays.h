@@ -4,7 +4,10 @@
  * cameras, optionally with radial-tangential lens undistortion, :409-493 and
  * :558-565; optional NDC conversion, camera_utils.convert_to_ndc :31-97).  One
  * thread per pixel; 8 B in (pixel coordinates), 56 B out per ray -- HBM-bound,
- * trivially so for the pinhole instantiation.
+ * trivially so for the pinhole instantiation.  image_rays_kernel below is the
+ * whole-frame form: pixel coordinates from the flat index, all nine Rays fields
+ * out (64 B per ray, nothing in), pinhole or spherical (cast_spherical_rays,
+ * :700-746).
  */
 #pragma once
 #include <hip/hip_runtime.h>
@@ -128,6 +131,125 @@ __global__ void pixels_to_rays_kernel(const RayGenArgs A) {
   }
   A.radii[i] = (0.5f * (dxn + dyn)) * 2.0f / sqrtf(12.0f);
   if (A.imageplane) { A.imageplane[(size_t)i * 2] = cam0[0]; A.imageplane[(size_t)i * 2 + 1] = cam0[1]; }
+}
+
+/* A whole frame's `Rays` from (width, height, camera, pose): Dataset.generate_ray_batch (internal/datasets.py:487-498)
+ * for the flat, row-major pixel range [first, first + count) -- no pixel-index input, all nine fields in one launch. */
+struct ImageRaysArgs {
+  int width, height;
+  long long first;          /* flat index of the first pixel of the range */
+  int count;
+  const float *pixtocam;    /* [3,3]; unused by the spherical instantiation */
+  const float *camtoworld;  /* [3,4]: the frame's pose */
+  const float *pixtocam_ndc; /* [3,3] or NULL (pinhole only) */
+  float near, far;
+  int cam_idx;
+  float *origins, *directions, *viewdirs, *radii;             /* required */
+  float *imageplane, *lossmult, *near_out, *far_out;          /* each may be NULL */
+  int *cam_idx_out;                                           /* may be NULL */
+  LensDistortion dist;      /* read by the distorted instantiation only */
+};
+
+/* kSpherical = false: the arithmetic of pixels_to_rays_kernel<kDistort>, expression for expression (the library is built
+ * with -ffp-contract=off, so the five ray fields are the same bits), on the pixel (x, y) of the flat index.
+ * kSpherical = true: camera_utils.cast_spherical_rays (:700-746): node (i, j) of the (height+1) x (width+1) grid looks along
+ * (-sin phi sin theta, cos phi, sin phi cos theta), theta = 2 pi j / width, phi = pi i / height; dx / dy are the
+ * differences to the j+1 / i+1 nodes.  The three directions and their differences are computed in double from the
+ * float32 pose and rounded at the store: |dx| is a difference of unit vectors 2 pi / width apart, and its float32
+ * cancellation error (6e-8 * width / 2 pi relative) would pass the generator's 2e-6 bar at a few hundred columns. */
+template <bool kSpherical, bool kDistort>
+__global__ void image_rays_kernel(const ImageRaysArgs A) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= A.count) return;
+  const long long flat = A.first + i;
+  const int py = (int)(flat / A.width), px = (int)(flat - (long long)py * A.width);
+  const float *c2w = A.camtoworld;
+  float o[3] = {c2w[3], c2w[7], c2w[11]};
+  float d_out[3], v_out[3], radius, ip[2];
+  if constexpr (kSpherical) {
+    const double kPi = 3.14159265358979323846;
+    const double th0 = px * (2.0 * kPi / A.width), th1 = px + 1 == A.width ? 2.0 * kPi : (px + 1) * (2.0 * kPi / A.width);
+    const double ph0 = py * (kPi / A.height), ph1 = py + 1 == A.height ? kPi : (py + 1) * (kPi / A.height);
+    const double st0 = sin(th0), ct0 = cos(th0), st1 = sin(th1), ct1 = cos(th1);
+    const double sp0 = sin(ph0), cp0 = cos(ph0), sp1 = sin(ph1), cp1 = cos(ph1);
+    const double cam[3][3] = {{-sp0 * st0, cp0, sp0 * ct0},      /* the node, its j+1 and its i+1 neighbour */
+                              {-sp0 * st1, cp0, sp0 * ct1},
+                              {-sp1 * st0, cp1, sp1 * ct0}};
+    double dir[3][3];
+#pragma unroll
+    for (int q = 0; q < 3; ++q)
+#pragma unroll
+      for (int r = 0; r < 3; ++r)
+        dir[q][r] = ((double)c2w[r * 4] * cam[q][0] + (double)c2w[r * 4 + 1] * cam[q][1]) + (double)c2w[r * 4 + 2] * cam[q][2];
+    double s1 = 0.0, s2 = 0.0;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const double a = dir[1][c] - dir[0][c], b = dir[2][c] - dir[0][c];
+      s1 += a * a; s2 += b * b;
+      d_out[c] = (float)dir[0][c];
+      v_out[c] = d_out[c];                                /* viewdirs = directions, not renormalised (:725) */
+    }
+    radius = (float)((0.5 * (sqrt(s1) + sqrt(s2))) * 2.0 / sqrt(12.0));
+    ip[0] = 0.0f; ip[1] = 0.0f;
+  } else {
+    const float *p2c = A.pixtocam;
+    const float x = (float)px, y = (float)py;
+    float dir[3][3], cam0[3];
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {                       /* the pixel and its +x / +y neighbours */
+      const float pd[3] = {x + (q == 1 ? 1.0f : 0.0f) + 0.5f, y + (q == 2 ? 1.0f : 0.0f) + 0.5f, 1.0f};
+      float cam[3];
+      mat3_vec(p2c, 3, pd, cam);
+      if constexpr (kDistort) {
+        undistort(A.dist, cam[0], cam[1]);
+        cam[2] = 1.0f;
+      }
+      cam[1] = -cam[1]; cam[2] = -cam[2];               /* OpenCV -> OpenGL */
+      if (q == 0) { cam0[0] = cam[0]; cam0[1] = cam[1]; cam0[2] = cam[2]; }
+      mat3_vec(c2w, 4, cam, dir[q]);
+    }
+    const float nrm = sqrtf((dir[0][0] * dir[0][0] + dir[0][1] * dir[0][1]) + dir[0][2] * dir[0][2]);
+    float dxn, dyn;
+    if (A.pixtocam_ndc == nullptr) {
+      float s1 = 0.0f, s2 = 0.0f;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const float a = dir[1][c] - dir[0][c], b = dir[2][c] - dir[0][c];
+        s1 += a * a; s2 += b * b;
+        d_out[c] = dir[0][c];
+      }
+      dxn = sqrtf(s1); dyn = sqrtf(s2);
+    } else {
+      float ox[3], oy[3], on[3], tmp[3];
+      to_ndc(o, dir[1], A.pixtocam_ndc, ox, tmp);
+      to_ndc(o, dir[2], A.pixtocam_ndc, oy, tmp);
+      to_ndc(o, dir[0], A.pixtocam_ndc, on, d_out);
+      float s1 = 0.0f, s2 = 0.0f;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const float a = ox[c] - on[c], b = oy[c] - on[c];
+        s1 += a * a; s2 += b * b;
+        o[c] = on[c];
+      }
+      dxn = sqrtf(s1); dyn = sqrtf(s2);
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v_out[c] = dir[0][c] / nrm;   /* from the world-space direction, before NDC */
+    radius = (0.5f * (dxn + dyn)) * 2.0f / sqrtf(12.0f);
+    ip[0] = cam0[0]; ip[1] = cam0[1];
+  }
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    A.origins[(size_t)i * 3 + c] = o[c];
+    A.directions[(size_t)i * 3 + c] = d_out[c];
+    A.viewdirs[(size_t)i * 3 + c] = v_out[c];
+  }
+  A.radii[i] = radius;
+  if (A.imageplane) { A.imageplane[(size_t)i * 2] = ip[0]; A.imageplane[(size_t)i * 2 + 1] = ip[1]; }
+  if (A.lossmult) A.lossmult[i] = 1.0f;
+  if (A.near_out) A.near_out[i] = A.near;
+  if (A.far_out) A.far_out[i] = A.far;
+  if (A.cam_idx_out) A.cam_idx_out[i] = A.cam_idx;
 }
 
 }  // namespace rn

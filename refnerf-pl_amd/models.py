@@ -905,3 +905,29 @@ def render_image(render_fn: Callable[[utils.Rays], Tuple[List[Mapping[Text, torc
         for k in keys:
             rendering[k] = [r[ray_idx.to(r.device)] for r in rendering[k]]
     return rendering
+
+
+def render_path(render_fn, cameras, config: configs.Config, out_dir: Optional[str] = None, verbose: bool = False):
+    """The loop of RefNeRFSystem.render (nerf_system.py:467-531) as a generator: for every view `idx` of `cameras`
+    (a datasets.PathCameras, or anything with `.size` and `generate_ray_batch(idx)`) that belongs to this job
+    (`idx % config.render_num_jobs == config.render_job_id`), cast the frame's rays, `render_image` them and yield
+    `(idx, rendering)`.  With `out_dir` the artefact set of `utils.write_render_outputs` is written first, named with the
+    index zero-padded to max(3, digits of size - 1), and a view whose own colour file and that of this job's next view
+    both exist already is skipped (a restarted job resumes where it stopped).  `render_fn(rays)` is the eval forward,
+    e.g. `lambda rays: model(rays, 1., True)`.  Video encoding is left to the caller."""
+    import os
+    zpad = max(3, len(str(cameras.size - 1)))
+    for idx in range(cameras.size):
+        if idx % config.render_num_jobs != config.render_job_id:
+            continue
+        idx_str = str(idx).zfill(zpad)
+        if out_dir is not None:
+            next_str = str(idx + config.render_num_jobs).zfill(zpad)
+            if all(os.path.exists(os.path.join(out_dir, f'color_{s}.png')) for s in (idx_str, next_str)):
+                continue
+        batch = cameras.generate_ray_batch(idx)
+        with torch.no_grad():
+            rendering = render_image(render_fn, batch.rays, config, verbose=verbose, device=batch.rays.origins.device)
+        if out_dir is not None:
+            utils.write_render_outputs(rendering, out_dir, idx_str)
+        yield idx, rendering

@@ -1,6 +1,9 @@
 """Step-function helpers the losses need on the host -- mirror of the reference's internal/stepfun.py
 searchsorted (:31-56), inner_outer (:67-80) and lossfun_outer (:83-89).  (The resampler of the same
 file, sample_intervals / invert_cdf, is inside the fused level kernel: rn::sample_intervals_wave.)
+integrate_weights / invert_cdf / sample (:134-206) and math.sorted_interp (math.py:88-111) are here in their general,
+dtype-preserving torch form for host-side callers -- camera_utils.generate_ellipse_path resamples its angles with
+`sample` on float64 -- and are not on the hot path.
 """
 import torch
 
@@ -41,6 +44,48 @@ def weight_to_pdf(t, w, eps=torch.finfo(torch.float32).eps ** 2):
 def pdf_to_weight(t, p):
     """stepfun.py:97-99."""
     return p * (t[..., 1:] - t[..., :-1])
+
+
+def sorted_interp(x, xp, fp):
+    """np.interp along the last axis for sorted `xp` / `fp` (math.py:88-111), in the dtype of the arguments: each x is
+    bracketed by the largest xp <= x and the smallest xp > x (the ends of `xp` where there is none), found with the
+    reference's comparison mask, and `fp` is interpolated linearly between them (0 / 0 -> 0, offset clipped to [0, 1])."""
+    below = x[..., None, :] >= xp[..., :, None]                      # [..., len(xp), len(x)]
+
+    def bracket(v):
+        lo = torch.where(below, v[..., None], v[..., :1, None]).amax(dim=-2)
+        hi = torch.where(~below, v[..., None], v[..., -1:, None]).amin(dim=-2)
+        return lo, hi
+    fp0, fp1 = bracket(fp)
+    xp0, xp1 = bracket(xp)
+    offset = torch.clip(torch.nan_to_num((x - xp0) / (xp1 - xp0), 0), 0, 1)
+    return fp0 + offset * (fp1 - fp0)
+
+
+def integrate_weights(w):
+    """CDF at the knots of a step function whose weights sum to 1 along the last axis: [..., n] -> [..., n + 1] that
+    starts at exactly 0 and ends at exactly 1 (stepfun.py:134-154).  Keeps the dtype and device of `w`."""
+    cw = torch.clamp(torch.cumsum(w[..., :-1], dim=-1), max=1)
+    end = cw.shape[:-1] + (1,)
+    return torch.cat([cw.new_zeros(end), cw, cw.new_ones(end)], dim=-1)
+
+
+def invert_cdf(u, t, w_logits):
+    """Invert the CDF of the step function (t, softmax(w_logits)) at u in [0, 1) (stepfun.py:157-165)."""
+    return sorted_interp(u, integrate_weights(torch.softmax(w_logits, dim=-1)), t)
+
+
+def sample(t, w_logits, num_samples, single_jitter=False, deterministic_center=False):
+    """`num_samples` deterministic samples of the piecewise-constant PDF (t [..., n+1] sorted, w_logits [..., n]):
+    the inverse CDF at a linspace of [0, 1 - eps], or at the bin centres of that linspace with `deterministic_center`
+    (stepfun.py:168-206; eps is float32's, as there).  General, dtype-preserving torch -- the render-path generator
+    calls it on float64; the float32 hot path is the fused refnerf_sample_intervals, which does not come through here."""
+    del single_jitter                        # only read with a random generator, which the reference's port never passes
+    eps = torch.finfo(torch.float32).eps
+    pad = 1 / (2 * num_samples) if deterministic_center else 0
+    # the reference draws u in float32 whatever the dtype of t; keep those values so float64 callers get its samples
+    u = torch.linspace(pad, 1. - pad - eps, num_samples, dtype=torch.float32, device=t.device).to(t.dtype)
+    return invert_cdf(torch.broadcast_to(u, t.shape[:-1] + (num_samples,)), t, w_logits)
 
 
 def max_dilate(t, w, dilation, domain=(-float('inf'), float('inf')), rows_per_block=512):
