@@ -441,6 +441,68 @@ int refnerf_image_rays(int32_t projection, int32_t width, int32_t height,
                        int64_t first, int32_t count, const refnerf_image_rays_out *out,
                        void *stream);
 
+/* Scene loaders (internal/datasets.py:519-708), the device stages.
+ *
+ * refnerf_prepare_images: a stack of decoded images d_src [n,H,W,C] (uint8, or
+ * float32 with src_is_f32) to the float32 arrays `_load_renderings` keeps:
+ * area downsample by `factor` (image.downsample: the mean of each factor x
+ * factor block, float32(sum) / float32(factor^2)), then
+ *   REFNERF_PREP_SCALE    mean / 255                      -> d_out [n,h,w,C]   (LLFF rgb, :636-637)
+ *   REFNERF_PREP_WHITE    C = 4: v = mean / 255, v_rgb * v_a + (1 - v_a)
+ *                                                         -> d_out [n,h,w,3], d_alpha [n,h,w] = v_a when not NULL
+ *                                                                              (Blender, :550, :567-570)
+ *   REFNERF_PREP_NORMALS  C >= 3: mean_rgb * 2 / 255 - 1  -> d_out [n,h,w,3]   (:557)
+ *   REFNERF_PREP_RAW      mean                            -> d_out [n,h,w,C]   (disparity TIFFs, :554)
+ * with h = H / factor, w = W / factor.  Every operation is rounded to float32
+ * on its own, in the reference's order, so uint8 sources reproduce its numpy
+ * arrays bit for bit: their block sums are exact integers, which is why
+ * factor^2 * 255 must stay below 2^24 (factor <= 256).  float32 sources are
+ * summed in double and rounded once.  All offsets are 64-bit.
+ * REFNERF_EINVAL: a NULL d_src / d_out, a non-positive size, C outside
+ * {1, 3, 4}, a factor outside [1, 256] or one that does not divide H and W, an
+ * unknown op, WHITE without C = 4, NORMALS with C = 1, d_alpha without WHITE,
+ * a float32 pointer that is not 4-byte aligned, or more than 2^39 outputs. */
+#define REFNERF_PREP_SCALE 0
+#define REFNERF_PREP_WHITE 1
+#define REFNERF_PREP_NORMALS 2
+#define REFNERF_PREP_RAW 3
+int refnerf_prepare_images(const void *d_src, int32_t src_is_f32, int64_t n, int32_t H, int32_t W,
+                           int32_t C, int32_t factor, int32_t op, float *d_out, float *d_alpha,
+                           void *stream);
+
+/* refnerf_train_batch: one training batch of `Dataset._next_train` /
+ * `_make_ray_batch` (:395-485) in one launch.  Patch p has its origin at pixel
+ * (d_px0[p], d_py0[p]) of camera d_cam[p] (cam_per_patch) or d_cam[0]
+ * ('single_image' batching); its patch_size^2 rays are the pixels (x0 + dx,
+ * y0 + dy), dy major.  Outputs are [n_patches, patch_size, patch_size, .]:
+ * the nine Rays fields (all required; origins, directions, viewdirs, radii and
+ * imageplane bit-identical to refnerf_pixels_to_rays[_distorted] on the same
+ * pixels and cameras; lossmult 1, near, far, cam_idx as given), d_rgb =
+ * d_images[cam, y, x], and d_out_disps / d_out_normals / d_out_alphas likewise
+ * from their stacks when both the stack and the output are given.  The camera
+ * is read inside the kernel: d_pixtocams is [3,3] or, with
+ * pixtocam_per_camera, [n_images,3,3]; d_camtoworlds [n_images,3,4].  Image
+ * and camera loads clamp their indices into the stacks.
+ * REFNERF_EINVAL: a NULL required pointer, a non-positive size, patch_size
+ * larger than the image, n_patches * patch_size^2 >= 2^31, an optional output
+ * without its stack (or the reverse), or a `distortion` that
+ * refnerf_pixels_to_rays_distorted refuses. */
+typedef struct refnerf_train_batch_args {
+  const void *d_px0, *d_py0, *d_cam;           /* int32, or int64 with index_is_int64 (the dtype torch.randint draws) */
+  int32_t index_is_int64, cam_per_patch, n_patches, patch_size;
+  int32_t n_images, height, width;
+  const float *d_images;                       /* [n_images,H,W,3] */
+  const float *d_disps, *d_normals, *d_alphas; /* [n_images,H,W], [n_images,H,W,3], [n_images,H,W]; each may be NULL */
+  const float *d_pixtocams, *d_camtoworlds, *d_pixtocam_ndc; /* d_pixtocam_ndc may be NULL */
+  int32_t pixtocam_per_camera;
+  float near, far;
+  const refnerf_lens_distortion *distortion;   /* NULL: pinhole */
+  refnerf_image_rays_out rays;
+  float *d_rgb;                                /* [.,3] */
+  float *d_out_disps, *d_out_normals, *d_out_alphas;
+} refnerf_train_batch_args;
+int refnerf_train_batch(const refnerf_train_batch_args *args, void *stream);
+
 /* Stage entry points (same device code as the fused kernel; used by the
  * parity tests and for drop-in use of the individual reference functions). */
 
@@ -749,7 +811,8 @@ int refnerf_vis_ray_panel(const double *d_lines_values, const double *d_lines_al
 enum { REFNERF_TIMER_FORWARD = 0,   /* the level kernel of refnerf_level_forward / _forward_train           */
        REFNERF_TIMER_BACKWARD = 1,  /* the per-sample backward kernel of refnerf_level_backward              */
        REFNERF_TIMER_WGRAD = 2,     /* its weight-gradient GEMM                                              */
-       REFNERF_TIMER_IMAGE = 3 };   /* one pair per image-evaluation entry, around all of its launches       */
+       REFNERF_TIMER_IMAGE = 3,     /* one pair per image-evaluation entry, around all of its launches       */
+       REFNERF_TIMER_DATASET = 4 }; /* the one kernel of refnerf_prepare_images / refnerf_train_batch        */
 int refnerf_set_timing(int enable);
 int refnerf_get_timing(double *total_ms, int64_t *launches);                         /* REFNERF_TIMER_FORWARD */
 int refnerf_get_timing_family(int family, double *total_ms, int64_t *launches);

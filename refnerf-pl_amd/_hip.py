@@ -88,6 +88,19 @@ class ImageRaysOut(C.Structure):
                                    "d_far", "d_cam_idx")]
 
 
+PREP_SCALE, PREP_WHITE, PREP_NORMALS, PREP_RAW = 0, 1, 2, 3   # REFNERF_PREP_*
+
+
+class TrainBatchArgs(C.Structure):
+    """refnerf_train_batch_args"""
+    _fields_ = ([(n, _FP) for n in ("d_px0", "d_py0", "d_cam")]
+                + [(n, C.c_int32) for n in ("index_is_int64", "cam_per_patch", "n_patches", "patch_size", "n_images", "height", "width")]
+                + [(n, _FP) for n in ("d_images", "d_disps", "d_normals", "d_alphas", "d_pixtocams", "d_camtoworlds", "d_pixtocam_ndc")]
+                + [("pixtocam_per_camera", C.c_int32), ("near", C.c_float), ("far", C.c_float),
+                   ("distortion", C.POINTER(LensDistortion)), ("rays", ImageRaysOut)]
+                + [(n, _FP) for n in ("d_rgb", "d_out_disps", "d_out_normals", "d_out_alphas")])
+
+
 class AdamCfg(C.Structure):
     """refnerf_adam_cfg: one Adam step's scalars, computed by the host in double."""
     _fields_ = [(n, C.c_double) for n in ("lr", "beta1", "beta2", "eps", "bias_correction1", "sqrt_bias_correction2",
@@ -201,6 +214,8 @@ def lib():
         L.refnerf_image_rays.argtypes = [C.c_int32, C.c_int32, C.c_int32, _FP, _FP, C.c_int32, C.c_int32, _FP,
                                          C.POINTER(LensDistortion), C.c_float, C.c_float, C.c_int64, C.c_int32,
                                          C.POINTER(ImageRaysOut), _FP]
+        L.refnerf_prepare_images.argtypes = [_FP, C.c_int32, C.c_int64] + [C.c_int32] * 5 + [_FP, _FP, _FP]
+        L.refnerf_train_batch.argtypes = [C.POINTER(TrainBatchArgs), _FP]
         L.refnerf_mlp_forward.argtypes = [_FP, C.POINTER(LevelCfg), _FP, _FP, C.c_int32, _FP, C.c_int32, C.c_int32,
                                           C.POINTER(LevelOut), _FP]
         L.refnerf_sample_intervals.argtypes = [_FP, _FP, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float,
@@ -441,6 +456,85 @@ def image_rays(projection, width, height, pixtocam, camtoworlds, frame, near, fa
                                    ptr(pixtocam_ndc), None if distortion is None else C.byref(distortion), float(near),
                                    float(far), first, count, C.byref(out), stream_ptr()))
     return res
+
+
+def prepare_images(src, op: int, factor: int = 1, return_alpha: bool = False):
+    """refnerf_prepare_images: a device stack [n,H,W,C] or [n,H,W] (uint8 or float32; any storage offset) -> the float32
+    stack the reference's loaders keep, in one launch: block mean over `factor`, then PREP_SCALE (/ 255), PREP_WHITE
+    (/ 255 and white background; with `return_alpha` also the alpha plane [n,h,w]), PREP_NORMALS (* 2 / 255 - 1) or
+    PREP_RAW (the mean alone).  The result has the source's rank; WHITE and NORMALS have 3 channels."""
+    require_device()
+    assert src.is_cuda and src.dtype in (torch.uint8, torch.float32) and src.dim() in (3, 4), "uint8 / float32 [n,H,W(,C)] on the device"
+    src = src.contiguous()
+    n, H, W = src.shape[:3]
+    Cn = src.shape[3] if src.dim() == 4 else 1
+    factor = int(factor)
+    if factor < 1 or H % factor or W % factor:
+        h = w = 1                                      # refused by the library, with its message
+    else:
+        h, w = H // factor, W // factor
+    c_out = 3 if op in (PREP_WHITE, PREP_NORMALS) else Cn
+    out = torch.empty((n, h, w, c_out) if src.dim() == 4 else (n, h, w), dtype=torch.float32, device=src.device)
+    alpha = torch.empty((n, h, w), dtype=torch.float32, device=src.device) if return_alpha else None
+    check(lib().refnerf_prepare_images(ptr(src), int(src.dtype == torch.float32), n, H, W, Cn, factor, int(op),
+                                       C.c_void_p(out.data_ptr()), None if alpha is None else C.c_void_p(alpha.data_ptr()),
+                                       stream_ptr()))
+    return (out, alpha) if return_alpha else out
+
+
+def train_batch(px0, py0, cam, patch_size, images, pixtocams, camtoworlds, near, far, pixtocam_ndc=None,
+                distortion: LensDistortion = None, disps=None, normals=None, alphas=None):
+    """refnerf_train_batch: one training batch in one launch.  `px0`, `py0` [P] patch origins, `cam` [P] or [1], all
+    three int32 or all three int64 (as torch.randint draws them: no conversion launch); `images` float32 [n,H,W,3] and the optional stacks `disps` [n,H,W], `normals` [n,H,W,3], `alphas` [n,H,W];
+    `pixtocams` float32 [3,3] | [n,3,3], `camtoworlds` float32 [n,3,4].  Returns (rays, gathered): two dicts of device
+    tensors shaped [P, patch, patch, .] -- the nine RAY_FIELDS, and 'rgb' plus whichever of 'disps' / 'normals' /
+    'alphas' were given (those three without a channel axis where the stack has none)."""
+    require_device()
+    f32 = lambda t, what: _check_t(t, torch.float32, what)  # noqa: E731
+    assert px0.dtype in (torch.int32, torch.int64), "px0, py0, cam: int32 or int64"
+    px0, py0, cam = (_check_t(t, px0.dtype, what) for t, what in ((px0, "px0"), (py0, "py0"), (cam, "cam")))
+    P, ps = px0.numel(), int(patch_size)
+    assert py0.numel() == P and cam.numel() in (1, P), "py0: [P]; cam: [P] or [1]"
+    images = f32(images, "images")
+    assert images.dim() == 4 and images.shape[3] == 3, "images: float32 [n,H,W,3]"
+    n, H, W = images.shape[:3]
+    p2c, c2w = f32(pixtocams, "pixtocams"), f32(camtoworlds, "camtoworlds")
+    assert tuple(c2w.shape) == (n, 3, 4), "camtoworlds: float32 [n,3,4]"
+    assert tuple(p2c.shape) in ((3, 3), (n, 3, 3)), "pixtocams: float32 [3,3] or [n,3,3]"
+    ndc = None if pixtocam_ndc is None else f32(pixtocam_ndc, "pixtocam_ndc")
+    assert ndc is None or tuple(ndc.shape) == (3, 3)
+    if not 0 < P * ps * ps < 2 ** 31:
+        raise ValueError(f"refnerf_train_batch: {P} patches of {ps}^2 rays outside (0, 2^31)")
+    dev, shape = images.device, (P, ps, ps)
+    a, rays, got = TrainBatchArgs(), {}, {}
+    a.d_px0, a.d_py0, a.d_cam = px0.data_ptr(), py0.data_ptr(), cam.data_ptr()
+    a.index_is_int64, a.cam_per_patch, a.n_patches, a.patch_size = int(px0.dtype == torch.int64), int(cam.numel() == P), P, ps
+    a.n_images, a.height, a.width = n, H, W
+    a.d_images, a.d_pixtocams, a.d_camtoworlds = images.data_ptr(), p2c.data_ptr(), c2w.data_ptr()
+    a.d_pixtocam_ndc = None if ndc is None else ndc.data_ptr()
+    a.pixtocam_per_camera, a.near, a.far = int(p2c.dim() == 3), float(near), float(far)
+    if distortion is not None:
+        a.distortion = C.pointer(distortion)
+    for name, w in zip(RAY_FIELDS, RAY_FIELD_WIDTHS):
+        rays[name] = torch.empty(shape + (w,), dtype=torch.int32 if name == "cam_idx" else torch.float32, device=dev)
+        setattr(a.rays, "d_" + name, rays[name].data_ptr())
+    got["rgb"] = torch.empty(shape + (3,), dtype=torch.float32, device=dev)
+    a.d_rgb = got["rgb"].data_ptr()
+    for name, stack, tail in (("disps", disps, ()), ("normals", normals, (3,)), ("alphas", alphas, ())):
+        if stack is None:
+            continue
+        stack = f32(stack, name)
+        assert tuple(stack.shape) == (n, H, W) + tail, f"{name}: float32 {(n, H, W) + tail}"
+        got[name] = torch.empty(shape + tail, dtype=torch.float32, device=dev)
+        setattr(a, "d_" + name, stack.data_ptr())
+        setattr(a, "d_out_" + name, got[name].data_ptr())
+    check(lib().refnerf_train_batch(C.byref(a), stream_ptr()))
+    return rays, got
+
+
+def _check_t(t, dtype, what):
+    assert torch.is_tensor(t) and t.is_cuda and t.dtype == dtype and t.is_contiguous(), f"{what}: contiguous {dtype} device tensor"
+    return t
 
 
 def mlp_forward(packed, cfg: LevelCfg, means, covs, viewdirs):
@@ -1043,7 +1137,7 @@ def set_timing(enable: bool):
     lib().refnerf_set_timing(int(enable))
 
 
-TIMER_FORWARD, TIMER_BACKWARD, TIMER_WGRAD, TIMER_IMAGE = 0, 1, 2, 3
+TIMER_FORWARD, TIMER_BACKWARD, TIMER_WGRAD, TIMER_IMAGE, TIMER_DATASET = 0, 1, 2, 3, 4
 
 
 def get_timing(family: int = TIMER_FORWARD):

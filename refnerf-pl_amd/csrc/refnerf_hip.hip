@@ -30,6 +30,7 @@
 #include "refnerf_wgrad.h"
 #include "refnerf_wgrad_bf16x3.h"
 #include "refnerf_rays.h"
+#include "refnerf_dataset.h"
 #include "refnerf_optim.h"
 #include "refnerf_regularisers.h"
 #include "refnerf_proposal.h"
@@ -979,6 +980,96 @@ int refnerf_image_rays(int32_t projection, int32_t width, int32_t height, const 
   }
   HIP_TRY(hipGetLastError());
   return REFNERF_OK;
+}
+
+int refnerf_prepare_images(const void *d_src, int32_t src_is_f32, int64_t n, int32_t H, int32_t W, int32_t C, int32_t factor,
+                           int32_t op, float *d_out, float *d_alpha, void *stream) {
+  const char *fn = "refnerf_prepare_images";
+  if (!d_src || !d_out) return fail(REFNERF_EINVAL, "%s: null pointer", fn);
+  if (n <= 0 || H <= 0 || W <= 0) return fail(REFNERF_EINVAL, "%s: n, H and W must be positive", fn);
+  if (C != 1 && C != 3 && C != 4) return fail(REFNERF_EINVAL, "%s: C must be 1, 3 or 4", fn);
+  if (factor < 1) return fail(REFNERF_EINVAL, "%s: factor must be at least 1", fn);
+  if (factor > 256) return fail(REFNERF_EINVAL, "%s: factor above 256 (a block sum of factor^2 bytes must stay below 2^24)", fn);
+  if (H % factor != 0 || W % factor != 0) {
+    char what[96];
+    snprintf(what, sizeof(what), "refnerf_prepare_images: factor %d does not evenly divide image shape (%d, %d)", factor, H, W);
+    return fail(REFNERF_EINVAL, "%s", what);
+  }
+  if (op < REFNERF_PREP_SCALE || op > REFNERF_PREP_RAW) return fail(REFNERF_EINVAL, "%s: unknown operation", fn);
+  if (op == REFNERF_PREP_WHITE && C != 4) return fail(REFNERF_EINVAL, "%s: REFNERF_PREP_WHITE needs C = 4", fn);
+  if (op == REFNERF_PREP_NORMALS && C < 3) return fail(REFNERF_EINVAL, "%s: REFNERF_PREP_NORMALS needs C >= 3", fn);
+  if (d_alpha && op != REFNERF_PREP_WHITE) return fail(REFNERF_EINVAL, "%s: d_alpha is written by REFNERF_PREP_WHITE only", fn);
+  if (((uintptr_t)d_out & 3u) || ((uintptr_t)d_alpha & 3u) || (src_is_f32 && ((uintptr_t)d_src & 3u)))
+    return fail(REFNERF_EINVAL, "%s: misaligned float32 pointer", fn);
+  rn::ImagePrepareArgs a{};
+  a.src = d_src; a.H = H; a.W = W; a.h = H / factor; a.w = W / factor; a.factor = factor; a.op = op;
+  a.out = d_out; a.alpha = d_alpha;
+  if (n > ((int64_t)1 << 39) / ((int64_t)a.h * a.w)) return fail(REFNERF_EINVAL, "%s: more than 2^39 output pixels", fn);
+  a.total = n * a.h * a.w;
+  hipStream_t st = (hipStream_t)stream;
+  long tslot;
+  { int trc = timer_begin(st, &tslot, REFNERF_TIMER_DATASET); if (trc) return trc; }
+  if (src_is_f32) {
+    if (C == 1) rn::launch_image_prepare<float, 1, false>(a, st);
+    else if (C == 3) rn::launch_image_prepare<float, 3, false>(a, st);
+    else rn::launch_image_prepare<float, 4, false>(a, st);
+  } else {
+    if (C == 1) rn::launch_image_prepare<uint8_t, 1, false>(a, st);
+    else if (C == 3) rn::launch_image_prepare<uint8_t, 3, false>(a, st);
+    else if (((uintptr_t)d_src & 3u) == 0) rn::launch_image_prepare<uint8_t, 4, true>(a, st);   /* whole pixels as 32-bit words */
+    else rn::launch_image_prepare<uint8_t, 4, false>(a, st);
+  }
+  HIP_TRY(hipGetLastError());
+  return timer_end(st, tslot);
+}
+
+int refnerf_train_batch(const refnerf_train_batch_args *args, void *stream) {
+  const char *fn = "refnerf_train_batch";
+  if (!args) return fail(REFNERF_EINVAL, "%s: null pointer", fn);
+  const refnerf_train_batch_args &g = *args;
+  const refnerf_image_rays_out &o = g.rays;
+  if (!g.d_px0 || !g.d_py0 || !g.d_cam || !g.d_images || !g.d_pixtocams || !g.d_camtoworlds || !g.d_rgb || !o.d_origins ||
+      !o.d_directions || !o.d_viewdirs || !o.d_radii || !o.d_imageplane || !o.d_lossmult || !o.d_near || !o.d_far || !o.d_cam_idx)
+    return fail(REFNERF_EINVAL, "%s: null pointer", fn);
+  if (g.n_patches <= 0 || g.patch_size <= 0 || g.n_images <= 0 || g.height <= 0 || g.width <= 0)
+    return fail(REFNERF_EINVAL, "%s: n_patches, patch_size, n_images, height and width must be positive", fn);
+  if (g.patch_size > g.height || g.patch_size > g.width) return fail(REFNERF_EINVAL, "%s: patch_size larger than the image", fn);
+  const int64_t n = (int64_t)g.n_patches * g.patch_size * g.patch_size;
+  if (n >= ((int64_t)1 << 31)) return fail(REFNERF_EINVAL, "%s: n_patches * patch_size^2 must be below 2^31", fn);
+  if ((g.d_disps == nullptr) != (g.d_out_disps == nullptr) || (g.d_normals == nullptr) != (g.d_out_normals == nullptr) ||
+      (g.d_alphas == nullptr) != (g.d_out_alphas == nullptr))
+    return fail(REFNERF_EINVAL, "%s: disps / normals / alphas need both the stack and the output", fn);
+  const refnerf_lens_distortion *dist = g.distortion;
+  if (dist) {
+    const double c[7] = {dist->k1, dist->k2, dist->k3, dist->k4, dist->p1, dist->p2, dist->eps};
+    for (double v : c)
+      if (!std::isfinite(v)) return fail(REFNERF_EINVAL, "%s: non-finite distortion parameter", fn);
+    if (dist->max_iterations < 0 || dist->max_iterations > REFNERF_MAX_UNDISTORT_ITERATIONS)
+      return fail(REFNERF_EINVAL, "%s: max_iterations must be in [0, 64]", fn);
+  }
+  rn::TrainBatchArgs a{};
+  a.px0 = g.d_px0; a.py0 = g.d_py0; a.cam = g.d_cam; a.idx64 = g.index_is_int64 ? 1 : 0; a.cam_stride = g.cam_per_patch ? 1 : 0;
+  a.ps = g.patch_size; a.n = (int)n;
+  a.n_images = g.n_images; a.H = g.height; a.W = g.width;
+  a.images = g.d_images; a.disps = g.d_disps; a.normals = g.d_normals; a.alphas = g.d_alphas;
+  a.pixtocams = g.d_pixtocams; a.p2c_stride = g.pixtocam_per_camera ? 9 : 0;
+  a.camtoworlds = g.d_camtoworlds; a.pixtocam_ndc = g.d_pixtocam_ndc;
+  a.near = g.near; a.far = g.far;
+  a.origins = o.d_origins; a.directions = o.d_directions; a.viewdirs = o.d_viewdirs; a.radii = o.d_radii;
+  a.imageplane = o.d_imageplane; a.lossmult = o.d_lossmult; a.near_out = o.d_near; a.far_out = o.d_far; a.cam_idx_out = o.d_cam_idx;
+  a.rgb = g.d_rgb; a.disps_out = g.d_out_disps; a.normals_out = g.d_out_normals; a.alphas_out = g.d_out_alphas;
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid((unsigned)((n + rn::DATASET_THREADS - 1) / rn::DATASET_THREADS)), block(rn::DATASET_THREADS);
+  long tslot;
+  { int trc = timer_begin(st, &tslot, REFNERF_TIMER_DATASET); if (trc) return trc; }
+  if (dist) {
+    a.dist = {dist->k1, dist->k2, dist->k3, dist->k4, dist->p1, dist->p2, dist->eps, dist->max_iterations};
+    hipLaunchKernelGGL(rn::train_batch_kernel<true>, grid, block, 0, st, a);
+  } else {
+    hipLaunchKernelGGL(rn::train_batch_kernel<false>, grid, block, 0, st, a);
+  }
+  HIP_TRY(hipGetLastError());
+  return timer_end(st, tslot);
 }
 
 int refnerf_mlp_forward(const void *d_packed, const refnerf_level_cfg *cfg, const float *d_means, const float *d_covs,

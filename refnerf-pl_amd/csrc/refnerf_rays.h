@@ -75,14 +75,14 @@ __device__ __forceinline__ void to_ndc(const float o_in[3], const float d[3], co
   for (int i = 0; i < 3; ++i) d_ndc[i] = inf[i] - o_ndc[i];
 }
 
-/* kDistort = false: the pinhole camera; true: undistort the camera-space points first (distortion_params, :558-565) */
+/* One perspective ray from the integer pixel (x, y), the body every pinhole generator shares (pixels_to_rays_kernel here,
+ * train_batch_kernel in refnerf_dataset.h), so that they agree bit for bit.  kDistort = false: the pinhole camera; true:
+ * undistort the camera-space points first (distortion_params, :558-565).  `p2c` [3,3], `c2w` [3,4], `ndc` [3,3] or NULL;
+ * `D` is read by the distorted instantiation only.  Out: origin, direction, viewdir, radius, imageplane (x, y). */
 template <bool kDistort>
-__global__ void pixels_to_rays_kernel(const RayGenArgs A) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= A.n) return;
-  const float *p2c = A.pixtocams + (size_t)i * A.p2c_stride;
-  const float *c2w = A.camtoworlds + (size_t)i * A.c2w_stride;
-  const float x = (float)A.pix_x[i], y = (float)A.pix_y[i];
+__device__ __forceinline__ void cast_pixel_ray(const float *p2c, const float *c2w, const float *ndc, const LensDistortion &D,
+                                               const float x, const float y, float o[3], float d_out[3], float v_out[3],
+                                               float &radius, float ip[2]) {
   float dir[3][3], cam0[3];
 #pragma unroll
   for (int q = 0; q < 3; ++q) {                       /* the pixel and its +x / +y neighbours */
@@ -90,17 +90,17 @@ __global__ void pixels_to_rays_kernel(const RayGenArgs A) {
     float cam[3];
     mat3_vec(p2c, 3, pd, cam);
     if constexpr (kDistort) {                         /* restacked with ones_like (:565) */
-      undistort(A.dist, cam[0], cam[1]);
+      undistort(D, cam[0], cam[1]);
       cam[2] = 1.0f;
     }
     cam[1] = -cam[1]; cam[2] = -cam[2];               /* OpenCV -> OpenGL */
     if (q == 0) { cam0[0] = cam[0]; cam0[1] = cam[1]; cam0[2] = cam[2]; }
     mat3_vec(c2w, 4, cam, dir[q]);
   }
-  float o[3] = {c2w[3], c2w[7], c2w[11]};
+  o[0] = c2w[3]; o[1] = c2w[7]; o[2] = c2w[11];
   const float nrm = sqrtf((dir[0][0] * dir[0][0] + dir[0][1] * dir[0][1]) + dir[0][2] * dir[0][2]);
-  float dxn, dyn, d_out[3];
-  if (A.pixtocam_ndc == nullptr) {
+  float dxn, dyn;
+  if (ndc == nullptr) {
     float s1 = 0.0f, s2 = 0.0f;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
@@ -111,9 +111,9 @@ __global__ void pixels_to_rays_kernel(const RayGenArgs A) {
     dxn = sqrtf(s1); dyn = sqrtf(s2);
   } else {
     float ox[3], oy[3], on[3], tmp[3];
-    to_ndc(o, dir[1], A.pixtocam_ndc, ox, tmp);
-    to_ndc(o, dir[2], A.pixtocam_ndc, oy, tmp);
-    to_ndc(o, dir[0], A.pixtocam_ndc, on, d_out);
+    to_ndc(o, dir[1], ndc, ox, tmp);
+    to_ndc(o, dir[2], ndc, oy, tmp);
+    to_ndc(o, dir[0], ndc, on, d_out);
     float s1 = 0.0f, s2 = 0.0f;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
@@ -124,13 +124,27 @@ __global__ void pixels_to_rays_kernel(const RayGenArgs A) {
     dxn = sqrtf(s1); dyn = sqrtf(s2);
   }
 #pragma unroll
+  for (int c = 0; c < 3; ++c) v_out[c] = dir[0][c] / nrm;   /* from the world-space direction, before NDC */
+  radius = (0.5f * (dxn + dyn)) * 2.0f / sqrtf(12.0f);
+  ip[0] = cam0[0]; ip[1] = cam0[1];
+}
+
+template <bool kDistort>
+__global__ void pixels_to_rays_kernel(const RayGenArgs A) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= A.n) return;
+  const float *p2c = A.pixtocams + (size_t)i * A.p2c_stride;
+  const float *c2w = A.camtoworlds + (size_t)i * A.c2w_stride;
+  float o[3], d_out[3], v_out[3], radius, ip[2];
+  cast_pixel_ray<kDistort>(p2c, c2w, A.pixtocam_ndc, A.dist, (float)A.pix_x[i], (float)A.pix_y[i], o, d_out, v_out, radius, ip);
+#pragma unroll
   for (int c = 0; c < 3; ++c) {
     A.origins[(size_t)i * 3 + c] = o[c];
     A.directions[(size_t)i * 3 + c] = d_out[c];
-    A.viewdirs[(size_t)i * 3 + c] = dir[0][c] / nrm;   /* from the world-space direction, before NDC */
+    A.viewdirs[(size_t)i * 3 + c] = v_out[c];
   }
-  A.radii[i] = (0.5f * (dxn + dyn)) * 2.0f / sqrtf(12.0f);
-  if (A.imageplane) { A.imageplane[(size_t)i * 2] = cam0[0]; A.imageplane[(size_t)i * 2 + 1] = cam0[1]; }
+  A.radii[i] = radius;
+  if (A.imageplane) { A.imageplane[(size_t)i * 2] = ip[0]; A.imageplane[(size_t)i * 2 + 1] = ip[1]; }
 }
 
 /* A whole frame's `Rays` from (width, height, camera, pose): Dataset.generate_ray_batch (internal/datasets.py:487-498)
