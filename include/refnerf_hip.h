@@ -614,6 +614,59 @@ typedef struct refnerf_noisy_rays_args {
 } refnerf_noisy_rays_args;
 int refnerf_noisy_rays(const refnerf_noisy_rays_args *args, void *stream);
 
+/* The data term of one level with either penalty, and its two statistics (internal/train_utils.py:33-88
+ * compute_data_loss; refnerf_losses_forward covers 'mse' without statistics only).  R flat rays.
+ * refnerf_data_terms_forward writes per-ray rows d_terms [R,5]:
+ *   0  sum_c lossmult (rgb_c - gt_c)^2                                  (the numerator of stats['mses'])
+ *   1  sum_c lossmult p_c, p = r^2 (REFNERF_PENALTY_MSE) or sqrt(r^2 + charb_padding^2) (REFNERF_PENALTY_CHARB; r^2 is
+ *      formed first and the squared padding added after, as the reference does)
+ *   2  (1 / (1 + distance_mean) - disps)^2                              (stats['disparity_mses'], :62-67)
+ *   3  w acos(clip(n_hat . ngt_hat, -(1 - 2^-23), 1 - 2^-23))           4  w = acc alphas       (stats['normal_maes'], :69-84)
+ * with x_hat = x / sqrt(max(sum x^2, 2^-23)) (ref_utils.py:40-50).  The caller sums the rows over the rays (one column
+ * sum: no float atomics, two runs give the same bits) and forms the normalisers on the device: 3 sum(lossmult) for columns
+ * 0 and 1, R for column 2, column 3 / column 4 times 180 / pi.  d_gt_rgb is the target the loss compares with (already
+ * linearised under Config.supervised_by_linear_rgb).  Optional groups: { d_distance_mean, d_disps } and { d_acc, d_alphas,
+ * d_normals, d_normals_gt }; an absent group leaves its columns 0.
+ * refnerf_data_terms_backward writes d_g_rgb [R,3] = d_upstream[0] lossmult (2 r | r / sqrt(r^2 + charb_padding^2));
+ * d_upstream is a DEVICE float (multiplier / normaliser x autograd's grad_output: no host synchronisation).  The statistics
+ * carry no gradient (the reference rebuilds them with torch.tensor).
+ * REFNERF_EINVAL: a null args / d_rgb / d_gt_rgb / d_lossmult / d_terms (forward) / d_upstream, d_g_rgb (backward), R <= 0,
+ * an unknown penalty, a negative or non-finite charb_padding, an optional group given in part. */
+enum { REFNERF_PENALTY_MSE = 0, REFNERF_PENALTY_CHARB = 1 };
+typedef struct refnerf_data_terms_args {
+  int32_t R, penalty;                          /* REFNERF_PENALTY_* */
+  float charb_padding;                         /* Config.charb_padding */
+  const float *d_rgb, *d_gt_rgb, *d_lossmult;  /* [R,3] renderings['rgb'], [R,3] target, [R] rays.lossmult */
+  const float *d_distance_mean, *d_disps;      /* [R] renderings['distance_mean'], [R] batch.disps */
+  const float *d_acc, *d_alphas, *d_normals, *d_normals_gt;   /* [R], [R], [R,3] renderings['normals'], [R,3] batch.normals */
+  float *d_terms;                              /* forward: [R,5] */
+  const float *d_upstream;                     /* backward: float[1] */
+  float *d_g_rgb;                              /* backward: [R,3] */
+} refnerf_data_terms_args;
+int refnerf_data_terms_forward(const refnerf_data_terms_args *args, void *stream);
+int refnerf_data_terms_backward(const refnerf_data_terms_args *args, void *stream);
+
+/* The edge-aware depth smoothness of one level of a patch batch (internal/train_utils.py:90-119
+ * compute_depth_smoothness_loss): P patches of S x S rays, d_distance [P,S,S], d_acc [P,S,S], d_rgb [P,S,S,3].
+ * refnerf_depth_smoothness_forward writes per-patch rows d_terms [P,2] =
+ *   { sum |acc00 w01 (v00 - v01)^2|, sum |acc00 w10 (v00 - v10)^2| } over the (S-1)^2 cells of the patch, 00 the cell's
+ * pixel, 01 its right and 10 its lower neighbour, w = exp(-mean_c |rgb00 - rgb_neighbour|).  The caller forms
+ * (column 0 + column 1) / (2 P (S-1)^2) and applies Config's coarse / fine multiplier on the device.
+ * refnerf_depth_smoothness_backward writes d_g_distance [P,S,S] in gather form (one thread per pixel, no atomics): the
+ * pixel's contribution as v00 of its own cell, as v01 of the cell to its left and as v10 of the cell above, times
+ * d_upstream[0] (a DEVICE float); the sign of the product is kept, as abs() does.  acc and rgb get no gradient (the
+ * reference reads them under no_grad).
+ * REFNERF_EINVAL: a null pointer, P <= 0, S < 2, P S S >= 2^31. */
+typedef struct refnerf_depth_smoothness_args {
+  int32_t P, S;
+  const float *d_distance, *d_acc, *d_rgb;
+  float *d_terms;                              /* forward: [P,2] */
+  const float *d_upstream;                     /* backward: float[1] */
+  float *d_g_distance;                         /* backward: [P,S,S] */
+} refnerf_depth_smoothness_args;
+int refnerf_depth_smoothness_forward(const refnerf_depth_smoothness_args *args, void *stream);
+int refnerf_depth_smoothness_backward(const refnerf_depth_smoothness_args *args, void *stream);
+
 /* The two host-side stages of the proposal-network configuration (num_levels = 3, a separate PropMLP, dilation and
  * interlevel loss on), one wave per ray, no host synchronisation, no allocation, every sum in one fixed order.
  *

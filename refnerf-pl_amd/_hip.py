@@ -130,6 +130,22 @@ class NoisyRaysArgs(C.Structure):
         ("d_" + n, _FP) for n in RAY_FIELDS] + [("d_out_" + n, _FP) for n in RAY_FIELDS]
 
 
+PENALTIES = {"mse": 0, "charb": 1}   # REFNERF_PENALTY_*
+
+
+class DataTermsArgs(C.Structure):
+    """refnerf_data_terms_args: one level's data term and statistics (None = optional group absent)."""
+    _fields_ = [("R", C.c_int32), ("penalty", C.c_int32), ("charb_padding", C.c_float)] + [(n, _FP) for n in (
+        "d_rgb", "d_gt_rgb", "d_lossmult", "d_distance_mean", "d_disps", "d_acc", "d_alphas", "d_normals", "d_normals_gt",
+        "d_terms", "d_upstream", "d_g_rgb")]
+
+
+class DepthSmoothnessArgs(C.Structure):
+    """refnerf_depth_smoothness_args: one level of a [P,S,S] patch batch."""
+    _fields_ = [("P", C.c_int32), ("S", C.c_int32)] + [(n, _FP) for n in (
+        "d_distance", "d_acc", "d_rgb", "d_terms", "d_upstream", "d_g_distance")]
+
+
 VIS_CURVES = {"none": 0, "neg_log": 1, "log": 2}      # REFNERF_VIS_CURVE_*
 VIS_OPS = {"none": 0, "clip01": 1, "sqrt": 2}         # REFNERF_VIS_OP_*
 VIS_MAX_PS, VIS_MAX_NORMALS = 8, 4
@@ -228,6 +244,10 @@ def lib():
         L.refnerf_ray_regularisers_forward.argtypes = [C.POINTER(RegularisersArgs), _FP]
         L.refnerf_ray_regularisers_backward.argtypes = [C.POINTER(RegularisersArgs), _FP]
         L.refnerf_noisy_rays.argtypes = [C.POINTER(NoisyRaysArgs), _FP]
+        L.refnerf_data_terms_forward.argtypes = [C.POINTER(DataTermsArgs), _FP]
+        L.refnerf_data_terms_backward.argtypes = [C.POINTER(DataTermsArgs), _FP]
+        L.refnerf_depth_smoothness_forward.argtypes = [C.POINTER(DepthSmoothnessArgs), _FP]
+        L.refnerf_depth_smoothness_backward.argtypes = [C.POINTER(DepthSmoothnessArgs), _FP]
         L.refnerf_max_dilate_weights.argtypes = [_FP, _FP, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, _FP, _FP, _FP]
         L.refnerf_interlevel_forward.argtypes = [_FP] * 4 + [C.c_int32] * 3 + [_FP, _FP]
         L.refnerf_interlevel_backward.argtypes = [_FP] * 4 + [C.c_int32] * 3 + [_FP, _FP, _FP]
@@ -761,6 +781,92 @@ def noisy_rays(rotations, distance, fields):
         setattr(A, "d_out_" + name, outs[-1].data_ptr())
     check(lib().refnerf_noisy_rays(C.byref(A), stream_ptr()))
     return outs
+
+
+def _checked_ptr(t, shape, dev, what):
+    """data pointer of a contiguous float32 tensor of exactly `shape` on `dev` (None passes through: an absent group)"""
+    if t is None:
+        return None
+    if not (t.is_cuda and t.device == dev and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == tuple(shape)):
+        raise ValueError(f"{what} must be a contiguous float32 tensor of shape {tuple(shape)} on {dev}")
+    return t.data_ptr()
+
+
+def _upstream_ptr(upstream, dev, what):
+    if not (upstream.is_cuda and upstream.device == dev and upstream.dtype == torch.float32 and upstream.is_contiguous() and
+            upstream.numel() == 1):
+        raise ValueError(f"{what}: upstream must be a float32 device tensor of one element")
+    return upstream.data_ptr()
+
+
+def data_terms_args(rgb, gt_rgb, lossmult, penalty, charb_padding, distance_mean=None, disps=None, acc=None, alphas=None,
+                    normals=None, normals_gt=None):
+    """DataTermsArgs over contiguous float32 device tensors, every shape checked here (the kernels trust them): rgb, gt_rgb
+    [R,3]; lossmult [R]; the disparity group distance_mean, disps [R]; the normal group acc, alphas [R] and normals,
+    normals_gt [R,3].  penalty: a key of PENALTIES.  The caller keeps the tensors alive while the struct is in use."""
+    if penalty not in PENALTIES:
+        raise ValueError(f"data terms: unknown penalty {penalty!r}")
+    dev, R = rgb.device, int(rgb.shape[0])
+    A = DataTermsArgs()
+    A.R, A.penalty, A.charb_padding = R, PENALTIES[penalty], float(charb_padding)
+    for name, t, shape in (("rgb", rgb, (R, 3)), ("gt_rgb", gt_rgb, (R, 3)), ("lossmult", lossmult, (R,)),
+                           ("distance_mean", distance_mean, (R,)), ("disps", disps, (R,)), ("acc", acc, (R,)),
+                           ("alphas", alphas, (R,)), ("normals", normals, (R, 3)), ("normals_gt", normals_gt, (R, 3))):
+        setattr(A, "d_" + name, _checked_ptr(t, shape, dev, "data terms: " + name))
+    return A
+
+
+def data_terms_forward(A: DataTermsArgs, device):
+    """refnerf_data_terms_forward on the arguments of data_terms_args -> terms [R,5] (see include/refnerf_hip.h)."""
+    require_device()
+    terms = torch.empty((max(int(A.R), 1), 5), dtype=torch.float32, device=device)
+    A.d_terms = terms.data_ptr()
+    check(lib().refnerf_data_terms_forward(C.byref(A), stream_ptr()))
+    return terms
+
+
+def data_terms_backward(A: DataTermsArgs, upstream):
+    """refnerf_data_terms_backward: upstream = one device float (multiplier / normaliser x grad_output) -> g_rgb [R,3]."""
+    require_device()
+    A.d_upstream = _upstream_ptr(upstream, upstream.device, "data terms")
+    g_rgb = torch.empty((max(int(A.R), 1), 3), dtype=torch.float32, device=upstream.device)
+    A.d_g_rgb = g_rgb.data_ptr()
+    check(lib().refnerf_data_terms_backward(C.byref(A), stream_ptr()))
+    return g_rgb
+
+
+def depth_smoothness_args(distance, acc, rgb):
+    """DepthSmoothnessArgs over contiguous float32 device tensors: distance, acc [P,S,S]; rgb [P,S,S,3] (shapes checked here)."""
+    dev = distance.device
+    if distance.ndim != 3 or distance.shape[1] != distance.shape[2]:
+        raise ValueError(f"depth smoothness: distance must be [P,S,S], got {tuple(distance.shape)}")
+    P, S = int(distance.shape[0]), int(distance.shape[1])
+    A = DepthSmoothnessArgs()
+    A.P, A.S = P, S
+    A.d_distance = _checked_ptr(distance, (P, S, S), dev, "depth smoothness: distance")
+    A.d_acc = _checked_ptr(acc, (P, S, S), dev, "depth smoothness: acc")
+    A.d_rgb = _checked_ptr(rgb, (P, S, S, 3), dev, "depth smoothness: rgb")
+    return A
+
+
+def depth_smoothness_forward(A: DepthSmoothnessArgs, device):
+    """refnerf_depth_smoothness_forward -> terms [P,2] (see include/refnerf_hip.h)."""
+    require_device()
+    terms = torch.empty((max(int(A.P), 1), 2), dtype=torch.float32, device=device)
+    A.d_terms = terms.data_ptr()
+    check(lib().refnerf_depth_smoothness_forward(C.byref(A), stream_ptr()))
+    return terms
+
+
+def depth_smoothness_backward(A: DepthSmoothnessArgs, upstream):
+    """refnerf_depth_smoothness_backward: upstream = one device float -> g_distance [P,S,S]."""
+    require_device()
+    A.d_upstream = _upstream_ptr(upstream, upstream.device, "depth smoothness")
+    P, S = max(int(A.P), 1), max(int(A.S), 1)
+    g = torch.empty((P, S, S), dtype=torch.float32, device=upstream.device)
+    A.d_g_distance = g.data_ptr()
+    check(lib().refnerf_depth_smoothness_backward(C.byref(A), stream_ptr()))
+    return g
 
 
 def _ptr32(t):

@@ -227,7 +227,7 @@ class Config:
     hip_train_precision: str = 'f32'  # MLP chains of the training forward: 'f32' (exact) | 'f16x2' (split f16: 22-bit products, parity-grade, ~3x faster) | 'bf16' (throughput mode)
     hip_bwd_precision: str = 'f32'  # transposed GEMM chains of the backward: 'f32' (exact) | 'f16x2' (split f16, parity-grade) | 'bf16' (throughput mode)
     hip_check_finite: bool = True  # train_utils.compute_losses watches every total loss (one device flag per step, read a step later: no synchronisation) and raises FloatingPointError on a non-finite one -- the operand-range limit of the 16-bit chains made loud
-    hip_fused_losses: bool = False  # data (mse) + orientation + predicted-normal losses of a level as ONE fused kernel each way (train_utils.fused_refnerf_losses)
+    hip_fused_losses: bool = False  # data ('mse' | 'charb', with the disparity / normal statistics) + orientation + predicted-normal losses of a level through fused kernels (train_utils.fused_refnerf_losses), and the depth smoothness of a [P, S, S, .] patch batch (train_utils.fused_depth_smoothness_loss)
     hip_fused_regularisers: bool = False  # the six geometry regularisers of a level (consistency x 4, accumulated weights, weights entropy) as ONE fused kernel each way and the noisy rays in one launch (train_utils.fused_ray_regularisers, sample_utils.sample_noisy_rays(fused=True)): no host synchronisation
     hip_fused_proposal: bool = False  # the proposal-network configuration's two host-side stages as kernels: the dilation of the step function between levels (models.Model.__call__ -> refnerf_max_dilate_weights) and the interlevel loss (train_utils.fused_interlevel_loss -> refnerf_interlevel_forward / _backward), one launch each, no host synchronisation
     hip_flat_grads: bool = False  # route the backward's gradient to MLP.flat_parameter().grad (one tensor) instead of the 46 nn.Parameters

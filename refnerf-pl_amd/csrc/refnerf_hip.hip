@@ -33,6 +33,7 @@
 #include "refnerf_dataset.h"
 #include "refnerf_optim.h"
 #include "refnerf_regularisers.h"
+#include "refnerf_data_terms.h"
 #include "refnerf_proposal.h"
 #include "refnerf_image.h"
 #include "refnerf_vis.h"
@@ -1458,6 +1459,70 @@ int refnerf_noisy_rays(const refnerf_noisy_rays_args *args, void *stream) {
   const size_t total = (size_t)args->n * args->a;
   if (total > (size_t)INT32_MAX) return fail(REFNERF_EINVAL, "refnerf_noisy_rays: n * a must be below 2^31%s");
   hipLaunchKernelGGL(rn::noisy_rays_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *args);
+  HIP_TRY(hipGetLastError());
+  return REFNERF_OK;
+}
+
+/* ---- the data term with either penalty, its statistics, and the patch depth smoothness (refnerf_data_terms.h) ---- */
+namespace {
+static int check_data_terms(const refnerf_data_terms_args *a, const char *fn) {
+  if (!a || !a->d_rgb || !a->d_gt_rgb || !a->d_lossmult) return fail(REFNERF_EINVAL, "%s: null pointer", fn);
+  if (a->R <= 0) return fail(REFNERF_EINVAL, "%s: R must be positive", fn);
+  if (a->penalty != REFNERF_PENALTY_MSE && a->penalty != REFNERF_PENALTY_CHARB)
+    return fail(REFNERF_EINVAL, "%s: unknown penalty (REFNERF_PENALTY_*)", fn);
+  if (!std::isfinite(a->charb_padding) || a->charb_padding < 0.0f)
+    return fail(REFNERF_EINVAL, "%s: charb_padding must be finite and not negative", fn);
+  /* an optional group is given whole or not at all */
+  if (!a->d_distance_mean != !a->d_disps)
+    return fail(REFNERF_EINVAL, "%s: the disparity statistic needs d_distance_mean and d_disps", fn);
+  const int n_normal = !!a->d_acc + !!a->d_alphas + !!a->d_normals + !!a->d_normals_gt;
+  if (n_normal != 0 && n_normal != 4)
+    return fail(REFNERF_EINVAL, "%s: the normal statistic needs d_acc, d_alphas, d_normals and d_normals_gt", fn);
+  return REFNERF_OK;
+}
+
+static int check_depth_smoothness(const refnerf_depth_smoothness_args *a, const char *fn) {
+  if (!a || !a->d_distance || !a->d_acc || !a->d_rgb) return fail(REFNERF_EINVAL, "%s: null pointer", fn);
+  if (a->P <= 0) return fail(REFNERF_EINVAL, "%s: P must be positive", fn);
+  if (a->S < 2) return fail(REFNERF_EINVAL, "%s: S must be at least 2", fn);
+  if ((int64_t)a->P * a->S * a->S >= ((int64_t)1 << 31)) return fail(REFNERF_EINVAL, "%s: P * S * S must be below 2^31", fn);
+  return REFNERF_OK;
+}
+}  // namespace
+
+int refnerf_data_terms_forward(const refnerf_data_terms_args *args, void *stream) {
+  const char *fn = "refnerf_data_terms_forward";
+  if (int rc = check_data_terms(args, fn)) return rc;
+  if (!args->d_terms) return fail(REFNERF_EINVAL, "%s: null pointer", fn);
+  hipLaunchKernelGGL(rn::data_terms_fwd_kernel, dim3((args->R + 255) / 256), dim3(256), 0, (hipStream_t)stream, *args);
+  HIP_TRY(hipGetLastError());
+  return REFNERF_OK;
+}
+
+int refnerf_data_terms_backward(const refnerf_data_terms_args *args, void *stream) {
+  const char *fn = "refnerf_data_terms_backward";
+  if (int rc = check_data_terms(args, fn)) return rc;
+  if (!args->d_upstream || !args->d_g_rgb) return fail(REFNERF_EINVAL, "%s: null pointer", fn);
+  hipLaunchKernelGGL(rn::data_terms_bwd_kernel, dim3((args->R + 255) / 256), dim3(256), 0, (hipStream_t)stream, *args);
+  HIP_TRY(hipGetLastError());
+  return REFNERF_OK;
+}
+
+int refnerf_depth_smoothness_forward(const refnerf_depth_smoothness_args *args, void *stream) {
+  const char *fn = "refnerf_depth_smoothness_forward";
+  if (int rc = check_depth_smoothness(args, fn)) return rc;
+  if (!args->d_terms) return fail(REFNERF_EINVAL, "%s: null pointer", fn);
+  hipLaunchKernelGGL(rn::depth_smoothness_fwd_kernel, dim3((args->P + 3) / 4), dim3(256), 0, (hipStream_t)stream, *args);
+  HIP_TRY(hipGetLastError());
+  return REFNERF_OK;
+}
+
+int refnerf_depth_smoothness_backward(const refnerf_depth_smoothness_args *args, void *stream) {
+  const char *fn = "refnerf_depth_smoothness_backward";
+  if (int rc = check_depth_smoothness(args, fn)) return rc;
+  if (!args->d_upstream || !args->d_g_distance) return fail(REFNERF_EINVAL, "%s: null pointer", fn);
+  const size_t n = (size_t)args->P * args->S * args->S;
+  hipLaunchKernelGGL(rn::depth_smoothness_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *args);
   HIP_TRY(hipGetLastError());
   return REFNERF_OK;
 }

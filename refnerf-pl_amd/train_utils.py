@@ -119,7 +119,8 @@ def predicted_normal_loss(model, ray_history, config):
 class _FusedRefNerfLosses(torch.autograd.Function):
     """data (mse) + orientation + predicted-normal loss of ONE level as a single autograd node on the fused kernels
     refnerf_losses_forward / refnerf_losses_backward (Config.hip_fused_losses): what compute_data_loss,
-    orientation_loss and predicted_normal_loss compute with ~25 elementwise ATen ops per level, in one pass each way."""
+    orientation_loss and predicted_normal_loss compute with ~25 elementwise ATen ops per level, in one pass each way.
+    (The 'charb' penalty and the statistics of compute_data_loss: _FusedDataTerms.)"""
 
     @staticmethod
     def forward(ctx, rgb, weights, normals_pred, aux):
@@ -153,19 +154,63 @@ class _FusedRefNerfLosses(torch.autograd.Function):
         return g_rgb, g_w, g_np, None
 
 
+class _FusedDataTerms(torch.autograd.Function):
+    """The data term of ONE level with either penalty ('mse' / 'charb') and the disparity / normal statistics of
+    compute_data_loss as a single autograd node on refnerf_data_terms_forward / _backward: returns (loss = scale x the
+    penalty's column sum, sums [5] = the kernel's column sums).  aux['scale'] is a device scalar (multiplier / normaliser),
+    so nothing is read back; the statistics are not differentiable, as in the reference."""
+
+    @staticmethod
+    def forward(ctx, rgb, aux):
+        from . import _hip
+        rgb_c = rgb.detach().to(torch.float32).reshape(-1, 3).contiguous()
+        args = _hip.data_terms_args(rgb_c, aux['gt'], aux['lossmult'], aux['penalty'], aux['charb_padding'], **aux['groups'])
+        sums = _hip.data_terms_forward(args, rgb_c.device).sum(dim=0)
+        ctx.set_materialize_grads(False)
+        ctx.args, ctx.keep, ctx.shape = args, (rgb_c, aux), rgb.shape     # keep: the tensors behind the struct's pointers
+        ctx.mark_non_differentiable(sums)
+        return sums[1] * aux['scale'], sums
+
+    @staticmethod
+    def backward(ctx, g_loss, _g_sums):
+        from . import _hip
+        if g_loss is None:
+            return None, None
+        # the upstream gradient times multiplier / normaliser, on the device (no host sync)
+        up = (g_loss.to(torch.float32) * ctx.keep[1]['scale']).reshape(1).contiguous()
+        return _hip.data_terms_backward(ctx.args, up).reshape(ctx.shape), None
+
+
 def fused_losses_supported(config):
-    """The fused path covers the loss set of the shipped refnerf configs: mse data term on the rendered rgb, orientation
-    and predicted-normal regularisers."""
-    return (config.data_loss_type == 'mse' and not config.supervised_by_linear_rgb and not config.compute_disp_metrics)
+    """The fused path covers both penalties of the data term ('mse', 'charb'), Config.supervised_by_linear_rgb and the
+    disparity / normal statistics, with the orientation and predicted-normal regularisers."""
+    return config.data_loss_type in ('mse', 'charb')
+
+
+def _fused_data_inputs_ok(batch, renderings, config):
+    """What the fused data term cannot take keeps the ATen path: a `disps` whose shape differs from distance_mean's (the
+    reference then broadcasts the two against each other), or renderings without distance_mean."""
+    if not config.compute_disp_metrics:
+        return True
+    disps = getattr(batch, 'disps', None)
+    return disps is not None and all(
+        'distance_mean' in r and tuple(np.shape(disps)) == tuple(r['distance_mean'].shape) for r in renderings)
 
 
 def fused_refnerf_losses(model, batch, rays, renderings, ray_history, config):
     """compute_data_loss + orientation_loss + predicted_normal_loss (train_utils.py:33-88,165-204) through the fused
     kernels: returns (data_loss, stats, orientation_loss, predicted_normal_loss) with the same values (fp32 summation
-    order aside) and the same gradients into renderings['rgb'], ray_history['weights'], ray_history['normals_pred']."""
+    order aside) and the same gradients into renderings['rgb'], ray_history['weights'], ray_history['normals_pred'].
+    An 'mse' data term without statistics rides in the node of the two regularisers (refnerf_losses_forward / _backward,
+    one launch each way per level); 'charb' or a statistic sends the data term of every level through _FusedDataTerms and
+    leaves the regularisers to that node.  stats carries 'mses', then 'disparity_mses', then 'normal_maes', each exactly
+    when compute_data_loss produces it; batch.disps / alphas / normals are taken flat."""
     dev = renderings[0]['rgb'].device
     f32 = dict(dtype=torch.float32, device=dev)
-    gt = torch.as_tensor(batch.rgb, **f32)[..., :3].reshape(-1, 3).contiguous()
+    gt = torch.as_tensor(batch.rgb, **f32)[..., :3]
+    if config.supervised_by_linear_rgb:
+        gt = srgb_to_linear(gt)                       # once per step, not once per level
+    gt = gt.reshape(-1, 3).contiguous()
     lossmult = torch.as_tensor(rays.lossmult, **f32).reshape(-1).contiguous()
     if config.disable_multiscale_loss:
         lossmult = torch.ones_like(lossmult)
@@ -175,10 +220,37 @@ def fused_refnerf_losses(model, batch, rays, renderings, ray_history, config):
     inv_denom = 1.0 / denom                           # stays on the device: no host synchronisation in the step
     want_o = _any_positive(config, 'orientation_coarse_loss_mult', 'orientation_loss_mult')
     want_n = _any_positive(config, 'predicted_normal_coarse_loss_mult', 'predicted_normal_loss_mult')
-    data, orient, normal, mses = [], [], [], []
+    want_disp, want_mae = bool(config.compute_disp_metrics), bool(config.compute_normal_metrics)
+    own_data_node = config.data_loss_type != 'mse' or want_disp or want_mae
+
+    def flat(x, *tail):
+        return torch.as_tensor(x, **f32).reshape((R,) + tail).contiguous()
+    disps = flat(batch.disps) if want_disp else None
+    if want_mae:
+        alphas, normals_gt = flat(batch.alphas), flat(batch.normals, 3)
+    data, orient, normal, mses, disp_mses, maes = [], [], [], [], [], []
     for i, (rendering, hist) in enumerate(zip(renderings, ray_history)):
         N = hist['weights'].shape[-1]
         fine = i == model.num_levels - 1
+        data_scale = (config.data_loss_mult if fine else config.data_coarse_loss_mult) * inv_denom
+        if own_data_node:
+            groups = {}
+            if want_disp:
+                groups.update(distance_mean=flat(rendering['distance_mean'].detach()), disps=disps)
+            if want_mae and 'normals' in rendering:
+                groups.update(acc=flat(rendering['acc'].detach()), alphas=alphas, normals=flat(rendering['normals'].detach(), 3),
+                              normals_gt=normals_gt)
+            loss, sums = _FusedDataTerms.apply(rendering['rgb'], dict(
+                gt=gt, lossmult=lossmult, penalty=config.data_loss_type, charb_padding=config.charb_padding, groups=groups,
+                scale=data_scale))
+            data.append(loss)
+            mses.append(sums[0] * inv_denom)
+            if want_disp:
+                disp_mses.append(sums[2] / R)
+            if want_mae:    # normals not computed (eval mode): NaN, as in the reference
+                maes.append(sums[3] / sums[4] * 180.0 / torch.pi if 'normals' in rendering else torch.full((), float('nan'), **f32))
+            if not (want_o or want_n):
+                continue
         orient_n = None
         if want_o:
             orient_n = hist[config.orientation_loss_target]
@@ -190,16 +262,23 @@ def fused_refnerf_losses(model, batch, rays, renderings, ray_history, config):
             if hist['normals'] is None or hist['normals_pred'] is None:
                 raise ValueError('Predicted normals and gradient normals cannot be None if predicted normal loss is on.')
             normals = hist['normals'].detach().reshape(R, N, 3).contiguous()
-        scales = torch.stack([(config.data_loss_mult if fine else config.data_coarse_loss_mult) * inv_denom,
+        scales = torch.stack([torch.zeros_like(inv_denom) if own_data_node else data_scale,
                               torch.full_like(inv_denom, (config.orientation_loss_mult if fine else config.orientation_coarse_loss_mult) / R),
                               torch.full_like(inv_denom, (config.predicted_normal_loss_mult if fine else config.predicted_normal_coarse_loss_mult) / R)])
         aux = dict(gt=gt, lossmult=lossmult, viewdirs=viewdirs, orient_n=orient_n, normals=normals, scales=scales,
                    orient_on_pred=config.orientation_loss_target == 'normals_pred')
-        _, per_term, sums = _FusedRefNerfLosses.apply(rendering['rgb'].reshape(R, 3), hist['weights'].reshape(R, N),
+        rgb = rendering['rgb'].detach() if own_data_node else rendering['rgb']      # detached: its data term is the other node's
+        _, per_term, sums = _FusedRefNerfLosses.apply(rgb.reshape(R, 3), hist['weights'].reshape(R, N),
                                                       hist['normals_pred'].reshape(R, N, 3), aux)
-        data.append(per_term[0]); orient.append(per_term[1]); normal.append(per_term[2])
-        mses.append(sums[0] * inv_denom)
+        orient.append(per_term[1]); normal.append(per_term[2])
+        if not own_data_node:
+            data.append(per_term[0])
+            mses.append(sums[0] * inv_denom)
     stats = {'mses': torch.stack([m.detach() for m in mses])}
+    if want_disp:
+        stats['disparity_mses'] = torch.stack([m.detach() for m in disp_mses])
+    if want_mae:
+        stats['normal_maes'] = torch.stack([m.detach() for m in maes])
     return (torch.stack(data).sum(), stats, torch.stack(orient).sum() if want_o else None,
             torch.stack(normal).sum() if want_n else None)
 
@@ -327,8 +406,9 @@ def fused_ray_regularisers(model, rays, noisy_rays, renderings, renderings_noise
     'diffuse_consistency', 'specular_consistency', 'normals_consistency', 'acc', 'distance_consistency' and
     'weights_entropy' that Config switches on, with the same values (fp32 summation order aside) and the same gradients into
     the clean and the noisy renderings and ray_history['weights'].  Flat batches ([R, .] rays) on the device; nothing is
-    read back to the host.  Depth smoothness (patch batches) stays ATen; the interlevel loss has its own kernels
-    (fused_interlevel_loss, Config.hip_fused_proposal)."""
+    read back to the host.  A patch batch ([P, S, S, .] rays) keeps the ATen regularisers; its depth smoothness has its own
+    kernels (fused_depth_smoothness_loss, Config.hip_fused_losses), as the interlevel loss has (fused_interlevel_loss,
+    Config.hip_fused_proposal)."""
     from . import _hip
     dev = renderings[0]['acc'].device
     f32 = dict(dtype=torch.float32, device=dev)
@@ -408,6 +488,56 @@ def compute_depth_smoothness_loss(renderings, config):
     per_level = torch.stack(per_level)
     return config.depth_smoothness_coarse_loss_mult * torch.sum(per_level[:-1]) + \
         config.depth_smoothness_loss_mult * per_level[-1]
+
+
+class _FusedDepthSmoothness(torch.autograd.Function):
+    """compute_depth_smoothness_loss of ONE level of a [P, S, S, .] patch batch as a single autograd node on
+    refnerf_depth_smoothness_forward / _backward: scale x (the two column sums of the per-patch rows), what ~30 ATen ops
+    and six [P, S-1, S-1, .] temporaries compute per level.  Only the distance gets a gradient (acc and the guide image
+    are read under no_grad in the reference); the upstream gradient stays on the device."""
+
+    @staticmethod
+    def forward(ctx, distance, acc, rgb, scale):
+        from . import _hip
+        P, S = acc.shape[0], acc.shape[1]
+        d_c, a_c = (t.detach().to(torch.float32).reshape(P, S, S).contiguous() for t in (distance, acc))
+        c_c = rgb.detach().to(torch.float32).reshape(P, S, S, 3).contiguous()
+        args = _hip.depth_smoothness_args(d_c, a_c, c_c)
+        sums = _hip.depth_smoothness_forward(args, d_c.device).sum(dim=0)
+        ctx.set_materialize_grads(False)
+        ctx.args, ctx.keep, ctx.scale, ctx.shape = args, (d_c, a_c, c_c), scale, distance.shape
+        return (sums[0] + sums[1]) * scale
+
+    @staticmethod
+    def backward(ctx, g_loss):
+        from . import _hip
+        if g_loss is None:
+            return None, None, None, None
+        up = (g_loss.to(torch.float32) * ctx.scale).reshape(1).contiguous()
+        return _hip.depth_smoothness_backward(ctx.args, up).reshape(ctx.shape), None, None, None
+
+
+def fused_depth_smoothness_supported(renderings):
+    """The kernels take CUDA renderings of one patch axis: acc [P, S, S], distance [P, S, S, 1], rgb [P, S, S, 3], S >= 2
+    (any other leading shape keeps the ATen path)."""
+    def ok(r):
+        acc = r['acc']
+        return (acc.is_cuda and acc.ndim == 3 and acc.shape[0] >= 1 and acc.shape[1] == acc.shape[2] >= 2 and
+                tuple(r['distance'].shape) == tuple(acc.shape) + (1,) and tuple(r['rgb'].shape) == tuple(acc.shape) + (3,))
+    return all(ok(r) for r in renderings)
+
+
+def fused_depth_smoothness_loss(renderings, config):
+    """compute_depth_smoothness_loss through the fused kernels, one autograd node per level: the same value (fp32 summation
+    order aside) and the same gradient into renderings['distance']."""
+    per_level = []
+    for i, rendering in enumerate(renderings):
+        P, S = rendering['acc'].shape[0], rendering['acc'].shape[1]
+        mult = config.depth_smoothness_loss_mult if i == len(renderings) - 1 else config.depth_smoothness_coarse_loss_mult
+        # (mean over the P (S-1)^2 cells of either edge + the same of the other) / 2
+        per_level.append(_FusedDepthSmoothness.apply(rendering['distance'], rendering['acc'], rendering['rgb'],
+                                                     mult / (2.0 * P * (S - 1) ** 2)))
+    return torch.stack(per_level).sum()                # coarse levels first, as the reference accumulates
 
 
 def _colour_consistency(kind, clean, noisy, mask):
@@ -551,10 +681,13 @@ def compute_losses(model, batch, rays, renderings, ray_history, config, renderin
     """The loss assembly of NeRFSystem.training_step (nerf_system.py:118-180) on already computed
     renderings: returns (total, dict of terms, stats).  Config.hip_fused_losses / hip_fused_regularisers route the three Ref-NeRF
     terms / the six geometry regularisers through their fused kernels and Config.hip_fused_proposal the interlevel loss through
-    its own (same keys, same order); depth smoothness stays ATen."""
+    its own (same keys, same order).  Config.hip_fused_losses also covers the 'charb' penalty, the linear-rgb target, the
+    disparity / normal statistics (the reference's stats keys in the reference's order) and the depth smoothness of a
+    [P, S, S, .] patch batch; the geometry regularisers want flat batches, so a patch batch keeps their ATen path."""
     losses = {}
-    fused = getattr(config, 'hip_fused_losses', False) and fused_losses_supported(config) and renderings[0]['rgb'].is_cuda
-    if fused:      # opt-in: the three Ref-NeRF terms of every level through refnerf_losses_forward / _backward
+    fused = (getattr(config, 'hip_fused_losses', False) and fused_losses_supported(config) and renderings[0]['rgb'].is_cuda and
+             _fused_data_inputs_ok(batch, renderings, config))
+    if fused:      # opt-in: the three Ref-NeRF terms of every level through refnerf_losses_* / refnerf_data_terms_*
         data_loss, stats, o_loss, n_loss = fused_refnerf_losses(model, batch, rays, renderings, ray_history, config)
     else:
         data_loss, stats = compute_data_loss(batch, renderings, rays, config)
@@ -568,7 +701,10 @@ def compute_losses(model, batch, rays, renderings, ray_history, config, renderin
     if _any_positive(config, 'predicted_normal_coarse_loss_mult', 'predicted_normal_loss_mult'):
         losses['predicted_normals'] = n_loss if fused else predicted_normal_loss(model, ray_history, config)
     if config.patch_size > 1 and _any_positive(config, 'depth_smoothness_coarse_loss_mult', 'depth_smoothness_loss_mult'):
-        losses['smoothness'] = compute_depth_smoothness_loss(renderings, config)
+        # opt-in: one launch each way per level (refnerf_depth_smoothness_forward / _backward) on one patch axis
+        fused_smooth = getattr(config, 'hip_fused_losses', False) and fused_depth_smoothness_supported(renderings)
+        losses['smoothness'] = fused_depth_smoothness_loss(renderings, config) if fused_smooth else \
+            compute_depth_smoothness_loss(renderings, config)
     want_distance = _any_positive(config, 'consistency_distance_loss_mult', 'consistency_distance_coarse_loss_mult')
     # opt-in: the six geometry regularisers of every level through refnerf_ray_regularisers_forward / _backward (flat batches on
     # the device; a missing noisy pass falls through to the ATen branches below and their ValueErrors)
