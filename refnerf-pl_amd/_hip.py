@@ -11,169 +11,67 @@ import subprocess
 
 import torch
 
+from . import _abi
+from ._abi import HipLibraryError  # noqa: F401
+
 _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB_PATH = os.path.join(_CSRC, "librefnerf_hip.so")
 if os.environ.get("REFNERF_LIB"):      # A/B builds of the library (scripts/build_*_variant.sh -> ab/*.so): a debug knob, never a fallback
     LIB_PATH = os.path.abspath(os.environ["REFNERF_LIB"])
 
-PREC_F32, PREC_BF16, PREC_F16, PREC_F16X2 = 0, 1, 2, 3
-IMAGE_F16X2_TRAIN = 4   # REFNERF_IMAGE_F16X2_TRAIN: the weight image of the REFNERF_PREC_F16X2 training kernels (built-in basis)
-ACT_F32, ACT_BF16, ACT_F16X2, ACT_SQ = 0, 1, 2, 3   # REFNERF_ACT_* (2 is retired: nothing writes or reads it)
-ABI_VERSION = 11  # REFNERF_ABI_VERSION
+# Every integer constant of the header under its name without the REFNERF_ prefix: ABI_VERSION, NUM_PARAMS, NUM_PARAMS_EXT,
+# PREC_*, IMAGE_F16X2_TRAIN, ACT_* (ACT_F16X2 = 2 is retired: nothing writes or reads it), WGRAD_*, DIRENC_*, PROJ_*, PREP_*,
+# TIMER_*, VIS_MAX_PS, VIS_MAX_NORMALS, ...
+globals().update({name[len("REFNERF_"):]: value for name, value in _abi.constants.items() if name.startswith("REFNERF_")})
+
+
+def _enum(prefix):
+    """{lower-case name: value} of the header's enumerators REFNERF_<prefix>_*: the strings the reference's configs use"""
+    prefix = "REFNERF_" + prefix + "_"
+    return {name[len(prefix):].lower(): value for name, value in _abi.constants.items() if name.startswith(prefix)}
+
+
+RAYDIST = _enum("RAYDIST")
+RAYDIST[None] = RAYDIST.pop("none")     # Model.raydist_fn = None
+SRGB_MODES = _enum("SRGB")
+CONSISTENCY_TYPES = _enum("CONSISTENCY")
+PENALTIES = _enum("PENALTY")
+VIS_CURVES = _enum("VIS_CURVE")
+VIS_OPS = _enum("VIS_OP")
 LEGACY_F16X2_TRAIN = False   # the round-4 training kernels (REFNERF_LEGACY_F16X2_TRAIN) are gone; bench.py still reads this name
-WGRAD_F32, WGRAD_BF16X3, WGRAD_F16 = 0, 1, 2
-DIRENC_IDE, DIRENC_POSENC = 0, 1   # REFNERF_DIRENC_*
-RAYDIST = {None: 0, "piecewise": 1, "reciprocal": 2, "log": 3, "exp": 4, "sqrt": 5, "square": 6}   # REFNERF_RAYDIST_*
-SRGB_MODES = {"none": 0, "linear": 1, "norm_linear": 2, "srgb": 3, "norm_srgb": 4}
+IPE_MAX_GROUPS = 7           # rn::IPE_MAX_GROUPS of the library: not part of the header
 
-_FP = C.c_void_p
-NUM_PARAMS = 1110158   # REFNERF_NUM_PARAMS
-NUM_PARAMS_EXT = NUM_PARAMS + 2 * 6 * 256 * 96   # REFNERF_NUM_PARAMS_EXT (general IPE basis: canonical blob + group tail)
-IPE_MAX_GROUPS = 7
-
-
-class LevelCfg(C.Structure):
-    _fields_ = [(n, C.c_int32) for n in (
-        "n_samples", "n_in", "training", "compute_extras", "srgb_mapping",
-        "srgb_mapping_normalization", "render_srgb_mode", "opaque_background",
-        "ray_shape", "precision", "wgrad_mode", "dir_enc", "raydist", "disable_integration", "ipe_groups")] + [(n, C.c_float) for n in (
-            "anneal", "resample_padding", "s_near", "s_far", "density_bias",
-            "roughness_bias", "rgb_premultiplier", "rgb_bias", "rgb_padding", "bg_rgb")]
-
-
-class RaysStruct(C.Structure):
-    _fields_ = [(n, _FP) for n in ("d_origins", "d_directions", "d_viewdirs", "d_radii", "d_near", "d_far")]
-
+# the header's argument structs (layouts checked against the C compiler in tests/test_abi.py)
+LevelCfg = _abi.structs["refnerf_level_cfg"]
+RaysStruct = _abi.structs["refnerf_rays"]
+LevelOut = _abi.structs["refnerf_level_out"]
+LevelOutExtra = _abi.structs["refnerf_level_out_extra"]
+LevelSaved = _abi.structs["refnerf_level_saved"]
+LevelGrads = _abi.structs["refnerf_level_grads"]
+LensDistortion = _abi.structs["refnerf_lens_distortion"]       # the keyword parameters of the reference's _radial_and_tangential_undistort
+ImageRaysOut = _abi.structs["refnerf_image_rays_out"]          # the nine utils.Rays fields
+TrainBatchArgs = _abi.structs["refnerf_train_batch_args"]
+AdamCfg = _abi.structs["refnerf_adam_cfg"]                     # one Adam step's scalars, computed by the host in double
+RegularisersArgs = _abi.structs["refnerf_regularisers_args"]   # sizes, thresholds, type enums, then one level's device pointers (None = term off)
+NoisyRaysArgs = _abi.structs["refnerf_noisy_rays_args"]
+DataTermsArgs = _abi.structs["refnerf_data_terms_args"]        # one level's data term and statistics (None = optional group absent)
+DepthSmoothnessArgs = _abi.structs["refnerf_depth_smoothness_args"]   # one level of a [P,S,S] patch batch
+VisPanelsArgs = _abi.structs["refnerf_vis_panels_args"]
+VisCmapArgs = _abi.structs["refnerf_vis_cmap_args"]
 
 OUT_FIELDS = ("d_sdist", "d_bin_idx", "d_density", "d_rgb", "d_normals", "d_normals_pred", "d_grad_pred",
               "d_tint", "d_diffuse", "d_specular", "d_roughness", "d_weights", "d_r_rgb", "d_r_diffuse",
               "d_r_specular", "d_r_distance", "d_r_acc", "d_r_normals", "d_r_normals_pred", "d_r_tint",
-              "d_r_roughness", "d_r_distance_mean", "d_r_percentiles")
-
-
-class LevelOut(C.Structure):
-    _fields_ = [(n, _FP) for n in OUT_FIELDS]
-
-
-OUT_EXTRA_FIELDS = ("d_r_percentiles_soa", "d_r_rgb_fg")
-
-
-class LevelOutExtra(C.Structure):
-    """refnerf_level_out_extra: the two per-ray outputs of the _ex level entries."""
-    _fields_ = [(n, _FP) for n in OUT_EXTRA_FIELDS]
-
-
-class LevelSaved(C.Structure):
-    _fields_ = [(n, _FP) for n in ("d_sdist", "d_density", "d_rgb", "d_weights", "d_activations")] + [
-        ("activations_format", C.c_int32)]
-
-
-class LevelGrads(C.Structure):
-    _fields_ = [(n, _FP) for n in ("d_g_r_rgb", "d_g_weights", "d_g_normals_pred", "d_g_r_acc", "d_g_r_distance",
-                                   "d_g_density", "d_g_rgb", "d_g_diffuse", "d_g_specular", "d_g_tint",
-                                   "d_g_roughness")]
-
-
-class LensDistortion(C.Structure):
-    """refnerf_lens_distortion: the keyword parameters of the reference's _radial_and_tangential_undistort."""
-    _fields_ = [(n, C.c_double) for n in ("k1", "k2", "k3", "k4", "p1", "p2", "eps")] + [("max_iterations", C.c_int32)]
-
-
-PROJ_PINHOLE, PROJ_SPHERICAL = 0, 1   # REFNERF_PROJ_*
-
-
-class ImageRaysOut(C.Structure):
-    """refnerf_image_rays_out: the nine utils.Rays fields."""
-    _fields_ = [(n, _FP) for n in ("d_origins", "d_directions", "d_viewdirs", "d_radii", "d_imageplane", "d_lossmult", "d_near",
-                                   "d_far", "d_cam_idx")]
-
-
-PREP_SCALE, PREP_WHITE, PREP_NORMALS, PREP_RAW = 0, 1, 2, 3   # REFNERF_PREP_*
-
-
-class TrainBatchArgs(C.Structure):
-    """refnerf_train_batch_args"""
-    _fields_ = ([(n, _FP) for n in ("d_px0", "d_py0", "d_cam")]
-                + [(n, C.c_int32) for n in ("index_is_int64", "cam_per_patch", "n_patches", "patch_size", "n_images", "height", "width")]
-                + [(n, _FP) for n in ("d_images", "d_disps", "d_normals", "d_alphas", "d_pixtocams", "d_camtoworlds", "d_pixtocam_ndc")]
-                + [("pixtocam_per_camera", C.c_int32), ("near", C.c_float), ("far", C.c_float),
-                   ("distortion", C.POINTER(LensDistortion)), ("rays", ImageRaysOut)]
-                + [(n, _FP) for n in ("d_rgb", "d_out_disps", "d_out_normals", "d_out_alphas")])
-
-
-class AdamCfg(C.Structure):
-    """refnerf_adam_cfg: one Adam step's scalars, computed by the host in double."""
-    _fields_ = [(n, C.c_double) for n in ("lr", "beta1", "beta2", "eps", "bias_correction1", "sqrt_bias_correction2",
-                                          "grad_max_val")] + [("write_grad", C.c_int32), ("no_step", C.c_int32)]
-
-
-CONSISTENCY_TYPES = {"mse": 0, "avg_mse": 1, "var": 2}   # REFNERF_CONSISTENCY_*
-
-
-class RegularisersArgs(C.Structure):
-    """refnerf_regularisers_args: sizes, thresholds and type enums, then the device pointers of one level (None = term off)."""
-    _fields_ = [(n, C.c_int32) for n in ("R", "S", "n", "a")] + [("thr_entropy", C.c_float), ("thr_consistency", C.c_float)] + [
-        (n, C.c_int32) for n in ("diffuse_type", "specular_type", "distance_type")] + [(n, _FP) for n in (
-            "d_weights", "d_acc", "d_distance", "d_diffuse", "d_specular", "d_normals", "d_n_distance", "d_n_diffuse",
-            "d_n_specular", "d_n_normals", "d_origins", "d_directions", "d_n_origins", "d_n_directions", "d_terms", "d_sums",
-            "d_scales", "d_g_weights", "d_g_acc", "d_g_distance", "d_g_diffuse", "d_g_specular", "d_g_normals",
-            "d_g_n_distance", "d_g_n_diffuse", "d_g_n_specular", "d_g_n_normals")]
-
-
+              "d_r_roughness", "d_r_distance_mean", "d_r_percentiles")                      # the fields of LevelOut
+OUT_EXTRA_FIELDS = ("d_r_percentiles_soa", "d_r_rgb_fg")                                    # the fields of LevelOutExtra
 RAY_FIELDS = ("origins", "directions", "viewdirs", "radii", "imageplane", "lossmult", "near", "far", "cam_idx")   # utils.Rays
 RAY_FIELD_WIDTHS = (3, 3, 3, 1, 2, 1, 1, 1, 1)
-
-
-class NoisyRaysArgs(C.Structure):
-    """refnerf_noisy_rays_args."""
-    _fields_ = [("n", C.c_int32), ("a", C.c_int32), ("d_rotations", _FP), ("d_distance", _FP)] + [
-        ("d_" + n, _FP) for n in RAY_FIELDS] + [("d_out_" + n, _FP) for n in RAY_FIELDS]
-
-
-PENALTIES = {"mse": 0, "charb": 1}   # REFNERF_PENALTY_*
-
-
-class DataTermsArgs(C.Structure):
-    """refnerf_data_terms_args: one level's data term and statistics (None = optional group absent)."""
-    _fields_ = [("R", C.c_int32), ("penalty", C.c_int32), ("charb_padding", C.c_float)] + [(n, _FP) for n in (
-        "d_rgb", "d_gt_rgb", "d_lossmult", "d_distance_mean", "d_disps", "d_acc", "d_alphas", "d_normals", "d_normals_gt",
-        "d_terms", "d_upstream", "d_g_rgb")]
-
-
-class DepthSmoothnessArgs(C.Structure):
-    """refnerf_depth_smoothness_args: one level of a [P,S,S] patch batch."""
-    _fields_ = [("P", C.c_int32), ("S", C.c_int32)] + [(n, _FP) for n in (
-        "d_distance", "d_acc", "d_rgb", "d_terms", "d_upstream", "d_g_distance")]
-
-
-VIS_CURVES = {"none": 0, "neg_log": 1, "log": 2}      # REFNERF_VIS_CURVE_*
-VIS_OPS = {"none": 0, "clip01": 1, "sqrt": 2}         # REFNERF_VIS_OP_*
-VIS_MAX_PS, VIS_MAX_NORMALS = 8, 4
 VIS_PANEL_INPUTS = ("d_rgb", "d_acc", "d_distance_mean", "d_distance_median", "d_distance_p5", "d_distance_p95", "d_origins",
                     "d_directions")
 VIS_PANEL_INPUTS_2 = ("d_roughness", "d_diffuse", "d_specular", "d_tint", "d_rgb_cc")
 VIS_PANEL_OUTPUTS = ("d_color", "d_acc_out", "d_color_matte", "d_depth_mean", "d_depth_median", "d_depth_triplet", "d_coords_mod")
 VIS_PANEL_OUTPUTS_2 = ("d_roughness_out", "d_diffuse_out", "d_diffuse_matte", "d_specular_out", "d_specular_matte", "d_tint_matte",
                        "d_color_corrected")
-
-
-class VisPanelsArgs(C.Structure):
-    """refnerf_vis_panels_args."""
-    _fields_ = [(n, C.c_int32) for n in ("H", "W", "f64", "linear_to_srgb", "table_n", "roughness_channels")] + [
-        (n, _FP) for n in ("d_table", "d_lohi_mean", "d_lohi_median", "d_lohi_triplet") + VIS_PANEL_INPUTS] + [
-        ("d_normals", _FP * VIS_MAX_NORMALS)] + [(n, _FP) for n in VIS_PANEL_INPUTS_2 + VIS_PANEL_OUTPUTS] + [
-        ("d_normals_out", _FP * VIS_MAX_NORMALS)] + [(n, _FP) for n in VIS_PANEL_OUTPUTS_2]
-
-
-class VisCmapArgs(C.Structure):
-    """refnerf_vis_cmap_args."""
-    _fields_ = [(n, C.c_int32) for n in ("H", "W", "channels", "f64", "out_f64", "curve", "normalise", "table_n")] + [
-        ("lo_bias", C.c_double), ("hi_bias", C.c_double), ("null_color", C.c_double * 3)] + [
-        (n, _FP) for n in ("d_values", "d_acc", "d_lo", "d_hi", "d_alpha", "d_table", "d_out")]
-
-
-class HipLibraryError(RuntimeError):
-    pass
 
 
 def build(force: bool = False) -> str:
@@ -195,90 +93,14 @@ def lib():
                 f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(the Ref-NeRF hot path has no CPU fallback)")
         L = C.CDLL(LIB_PATH)
-        L.refnerf_last_error.restype = C.c_char_p
-        L.refnerf_packed_weights_bytes.restype = C.c_size_t
-        L.refnerf_packed_weights_bytes.argtypes = [C.c_int]
-        L.refnerf_pack_weights.argtypes = [_FP, _FP, C.c_int, _FP]
-        L.refnerf_packed_weights_bytes_basis.restype = C.c_size_t
-        L.refnerf_packed_weights_bytes_basis.argtypes = [C.c_int, C.c_int]
-        L.refnerf_pack_weights_basis.argtypes = [_FP, _FP, C.c_int, _FP, C.c_int, _FP]
-        L.refnerf_level_forward.argtypes = [_FP, C.POINTER(LevelCfg), C.POINTER(RaysStruct), C.c_int32,
-                                            _FP, _FP, C.POINTER(LevelOut), _FP]
-        L.refnerf_level_forward_ex.argtypes = [_FP, C.POINTER(LevelCfg), C.POINTER(RaysStruct), C.c_int32,
-                                               _FP, _FP, C.POINTER(LevelOut), C.POINTER(LevelOutExtra), _FP]
-        L.refnerf_activations_format.argtypes = [C.POINTER(LevelCfg)]
-        L.refnerf_level_image.argtypes = [C.POINTER(LevelCfg)]
-        L.refnerf_level_image.restype = C.c_int
-        L.refnerf_activation_workspace_bytes.restype = C.c_size_t
-        L.refnerf_activation_workspace_bytes.argtypes = [C.c_int32, C.c_int32]
-        L.refnerf_level_forward_train.argtypes = [_FP, C.POINTER(LevelCfg), C.POINTER(RaysStruct), C.c_int32,
-                                                  _FP, _FP, C.POINTER(LevelOut), _FP, C.c_size_t, _FP]
-        L.refnerf_level_forward_train_ex.argtypes = [_FP, C.POINTER(LevelCfg), C.POINTER(RaysStruct), C.c_int32,
-                                                     _FP, _FP, C.POINTER(LevelOut), C.POINTER(LevelOutExtra), _FP, C.c_size_t, _FP]
-        L.refnerf_backward_workspace_bytes.restype = C.c_size_t
-        L.refnerf_backward_workspace_bytes_basis.restype = C.c_size_t
-        L.refnerf_backward_workspace_bytes_basis.argtypes = [C.c_int32, C.c_int32, C.c_int32]
-        L.refnerf_activation_workspace_bytes_basis.restype = C.c_size_t
-        L.refnerf_activation_workspace_bytes_basis.argtypes = [C.c_int32, C.c_int32, C.c_int32]
-        L.refnerf_backward_workspace_bytes.argtypes = [C.c_int32, C.c_int32]
-        L.refnerf_level_backward.argtypes = [_FP, C.POINTER(LevelCfg), C.POINTER(RaysStruct), C.c_int32,
-                                             C.POINTER(LevelSaved), C.POINTER(LevelGrads), _FP, _FP, C.c_size_t, _FP]
-        L.refnerf_pixels_to_rays.argtypes = [_FP, _FP, _FP, C.c_int32, _FP, C.c_int32, _FP, C.c_int32,
-                                             _FP, _FP, _FP, _FP, _FP, _FP]
-        L.refnerf_pixels_to_rays_distorted.argtypes = [_FP, _FP, _FP, C.c_int32, _FP, C.c_int32, _FP, C.c_int32,
-                                                       _FP, _FP, _FP, _FP, _FP, C.POINTER(LensDistortion), _FP]
-        L.refnerf_image_rays.argtypes = [C.c_int32, C.c_int32, C.c_int32, _FP, _FP, C.c_int32, C.c_int32, _FP,
-                                         C.POINTER(LensDistortion), C.c_float, C.c_float, C.c_int64, C.c_int32,
-                                         C.POINTER(ImageRaysOut), _FP]
-        L.refnerf_prepare_images.argtypes = [_FP, C.c_int32, C.c_int64] + [C.c_int32] * 5 + [_FP, _FP, _FP]
-        L.refnerf_train_batch.argtypes = [C.POINTER(TrainBatchArgs), _FP]
-        L.refnerf_mlp_forward.argtypes = [_FP, C.POINTER(LevelCfg), _FP, _FP, C.c_int32, _FP, C.c_int32, C.c_int32,
-                                          C.POINTER(LevelOut), _FP]
-        L.refnerf_sample_intervals.argtypes = [_FP, _FP, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float,
-                                               _FP, _FP, _FP]
-        L.refnerf_integrated_pos_enc.argtypes = [_FP, _FP, C.c_int32, _FP, _FP]
-        L.refnerf_integrated_dir_enc.argtypes = [_FP, _FP, C.c_int32, _FP, _FP]
-        L.refnerf_render_rays.argtypes = [C.POINTER(LevelCfg), C.c_int32] + [_FP] * 11 + [C.POINTER(LevelOut), _FP]
-        L.refnerf_losses_forward.argtypes = [C.c_int32, C.c_int32] + [_FP] * 9 + [_FP]
-        L.refnerf_losses_backward.argtypes = [C.c_int32, C.c_int32] + [_FP] * 5 + [C.c_int32] + [_FP] * 3 + [C.c_float] * 3 + [_FP] * 4 + [_FP]
-        L.refnerf_ray_regularisers_forward.argtypes = [C.POINTER(RegularisersArgs), _FP]
-        L.refnerf_ray_regularisers_backward.argtypes = [C.POINTER(RegularisersArgs), _FP]
-        L.refnerf_noisy_rays.argtypes = [C.POINTER(NoisyRaysArgs), _FP]
-        L.refnerf_data_terms_forward.argtypes = [C.POINTER(DataTermsArgs), _FP]
-        L.refnerf_data_terms_backward.argtypes = [C.POINTER(DataTermsArgs), _FP]
-        L.refnerf_depth_smoothness_forward.argtypes = [C.POINTER(DepthSmoothnessArgs), _FP]
-        L.refnerf_depth_smoothness_backward.argtypes = [C.POINTER(DepthSmoothnessArgs), _FP]
-        L.refnerf_max_dilate_weights.argtypes = [_FP, _FP, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, _FP, _FP, _FP]
-        L.refnerf_interlevel_forward.argtypes = [_FP] * 4 + [C.c_int32] * 3 + [_FP, _FP]
-        L.refnerf_interlevel_backward.argtypes = [_FP] * 4 + [C.c_int32] * 3 + [_FP, _FP, _FP]
-        L.refnerf_optim_workspace_bytes.restype = C.c_size_t
-        L.refnerf_optim_workspace_bytes.argtypes = [C.c_int64, C.c_int32]
-        L.refnerf_optim_state_bytes.restype = C.c_size_t
-        L.refnerf_optim_state_bytes.argtypes = [C.c_int32]
-        L.refnerf_optim_plan.argtypes = [C.c_int64, C.POINTER(C.c_int32), C.c_int32, _FP, C.c_size_t, C.POINTER(C.c_int32), _FP]
-        L.refnerf_optim_stats.argtypes = [_FP, _FP, C.c_int64, C.c_int32, C.c_int32, C.c_double, _FP, C.c_size_t, _FP,
-                                          _FP, C.c_size_t, C.c_int32, _FP]
-        L.refnerf_optim_finalize.argtypes = [_FP, C.c_size_t, C.c_int32, C.c_double, _FP]
-        L.refnerf_optim_adam_step.argtypes = [_FP, _FP, _FP, _FP, C.c_int64, C.POINTER(AdamCfg), _FP, _FP]
-        L.refnerf_image_workspace_bytes.restype = C.c_size_t
-        L.refnerf_image_workspace_bytes.argtypes = [C.c_int32] * 3
-        L.refnerf_image_mse.argtypes = [_FP, C.c_int64, _FP, C.c_int64] + [C.c_int32] * 4 + [_FP, _FP, C.c_size_t, _FP]
-        L.refnerf_image_ssim.argtypes = [_FP, C.c_int64, _FP, C.c_int64] + [C.c_int32] * 4 + [_FP, _FP, _FP, C.c_size_t, _FP]
-        L.refnerf_color_correct.argtypes = [_FP, C.c_int64, _FP, C.c_int64] + [C.c_int32] * 4 + [C.c_double, _FP, _FP, _FP,
-                                                                                                  C.c_size_t, _FP]
-        L.refnerf_weighted_mae.argtypes = [_FP, _FP, _FP, C.c_int64, _FP, _FP, C.c_size_t, _FP]
-        L.refnerf_vis_percentile_workspace_bytes.restype = C.c_size_t
-        L.refnerf_vis_percentile_workspace_bytes.argtypes = [C.c_int64]
-        L.refnerf_vis_weighted_percentile.argtypes = [_FP, C.c_int32, _FP, C.c_int32, C.c_int64, _FP, _FP, C.c_int64,
-                                                      C.POINTER(C.c_double), C.c_int32, C.c_int32, _FP, _FP, C.c_size_t, _FP]
-        L.refnerf_vis_panels.argtypes = [C.POINTER(VisPanelsArgs), _FP]
-        L.refnerf_vis_cmap.argtypes = [C.POINTER(VisCmapArgs), _FP]
-        L.refnerf_vis_resample_rays.argtypes = [_FP, _FP, _FP] + [C.c_int32] * 4 + [_FP] + [C.c_int32] * 3 + [C.c_int64, _FP, _FP, _FP]
-        L.refnerf_vis_ray_panel.argtypes = [_FP, _FP] + [C.c_int32] * 5 + [C.c_double, _FP, _FP, _FP, _FP]
-        L.refnerf_get_timing.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_int64)]
-        L.refnerf_get_timing_family.argtypes = [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
-        if L.refnerf_abi_version() != ABI_VERSION:
-            raise HipLibraryError("librefnerf_hip.so ABI version mismatch")
+        for name, (restype, argtypes) in _abi.prototypes.items():
+            try:
+                fn = getattr(L, name)
+            except AttributeError:
+                raise HipLibraryError(f"{LIB_PATH} does not export {name}, which {_abi.HEADER} declares: rebuild the library") from None
+            fn.restype, fn.argtypes = restype, argtypes
+        if L.refnerf_abi_version() != ABI_VERSION:      # the loaded library against the header
+            raise HipLibraryError(f"librefnerf_hip.so ABI version mismatch: {LIB_PATH} is not built from {_abi.HEADER}")
         _lib = L
     return _lib
 
@@ -308,6 +130,33 @@ def ptr(t):
         return None
     assert t.is_cuda and t.is_contiguous(), "device-resident contiguous tensor required"
     return C.c_void_p(t.data_ptr())
+
+
+def _arg(t, what, *, dtype=torch.float32, shape=None, numel=None, device=None, optional=False, empty_null=False, exc=ValueError):
+    """The checked tensor argument: the data pointer of a contiguous device tensor of `dtype` -- of exactly `shape`, of `numel`
+    elements, on `device`, where those are given -- or `exc` saying what `what` is instead.  optional: None passes through
+    (an absent argument); empty_null: an empty tensor gives None (the library launches nothing then).  (`ptr` is the trusting
+    pointer, for tensors this module made itself.)"""
+    if t is None and optional:
+        return None
+    if not torch.is_tensor(t):
+        raise exc(f"{what}: a tensor is required, not {type(t).__name__}")
+    bad = []
+    if t.dtype != dtype:
+        bad.append(f"is {t.dtype}, not {dtype}")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        bad.append(f"has shape {tuple(t.shape)}, not {tuple(shape)}")
+    if numel is not None and t.numel() != numel:
+        bad.append(f"has {t.numel()} elements, not {numel}")
+    if not t.is_contiguous():
+        bad.append("is not contiguous")
+    if not t.is_cuda:
+        bad.append("is not on a HIP device")
+    elif device is not None and t.device != device:
+        bad.append(f"is on {t.device}, not {device}")
+    if bad:
+        raise exc(f"{what} " + ", ".join(bad))
+    return None if empty_null and not t.numel() else t.data_ptr()
 
 
 def default_cfg(**kw) -> LevelCfg:
@@ -510,29 +359,24 @@ def train_batch(px0, py0, cam, patch_size, images, pixtocams, camtoworlds, near,
     tensors shaped [P, patch, patch, .] -- the nine RAY_FIELDS, and 'rgb' plus whichever of 'disps' / 'normals' /
     'alphas' were given (those three without a channel axis where the stack has none)."""
     require_device()
-    f32 = lambda t, what: _check_t(t, torch.float32, what)  # noqa: E731
+    a, rays, got = TrainBatchArgs(), {}, {}
     assert px0.dtype in (torch.int32, torch.int64), "px0, py0, cam: int32 or int64"
-    px0, py0, cam = (_check_t(t, px0.dtype, what) for t, what in ((px0, "px0"), (py0, "py0"), (cam, "cam")))
+    a.d_px0, a.d_py0, a.d_cam = (_arg(t, what, dtype=px0.dtype, exc=AssertionError) for t, what in ((px0, "px0"), (py0, "py0"), (cam, "cam")))
     P, ps = px0.numel(), int(patch_size)
     assert py0.numel() == P and cam.numel() in (1, P), "py0: [P]; cam: [P] or [1]"
-    images = f32(images, "images")
+    a.d_images = _arg(images, "images", exc=AssertionError)
     assert images.dim() == 4 and images.shape[3] == 3, "images: float32 [n,H,W,3]"
     n, H, W = images.shape[:3]
-    p2c, c2w = f32(pixtocams, "pixtocams"), f32(camtoworlds, "camtoworlds")
-    assert tuple(c2w.shape) == (n, 3, 4), "camtoworlds: float32 [n,3,4]"
-    assert tuple(p2c.shape) in ((3, 3), (n, 3, 3)), "pixtocams: float32 [3,3] or [n,3,3]"
-    ndc = None if pixtocam_ndc is None else f32(pixtocam_ndc, "pixtocam_ndc")
-    assert ndc is None or tuple(ndc.shape) == (3, 3)
+    a.d_pixtocams, a.d_camtoworlds = _arg(pixtocams, "pixtocams", exc=AssertionError), _arg(camtoworlds, "camtoworlds", exc=AssertionError)
+    assert tuple(camtoworlds.shape) == (n, 3, 4), "camtoworlds: float32 [n,3,4]"
+    assert tuple(pixtocams.shape) in ((3, 3), (n, 3, 3)), "pixtocams: float32 [3,3] or [n,3,3]"
+    a.d_pixtocam_ndc = _arg(pixtocam_ndc, "pixtocam_ndc", shape=(3, 3), optional=True, exc=AssertionError)
     if not 0 < P * ps * ps < 2 ** 31:
         raise ValueError(f"refnerf_train_batch: {P} patches of {ps}^2 rays outside (0, 2^31)")
     dev, shape = images.device, (P, ps, ps)
-    a, rays, got = TrainBatchArgs(), {}, {}
-    a.d_px0, a.d_py0, a.d_cam = px0.data_ptr(), py0.data_ptr(), cam.data_ptr()
     a.index_is_int64, a.cam_per_patch, a.n_patches, a.patch_size = int(px0.dtype == torch.int64), int(cam.numel() == P), P, ps
     a.n_images, a.height, a.width = n, H, W
-    a.d_images, a.d_pixtocams, a.d_camtoworlds = images.data_ptr(), p2c.data_ptr(), c2w.data_ptr()
-    a.d_pixtocam_ndc = None if ndc is None else ndc.data_ptr()
-    a.pixtocam_per_camera, a.near, a.far = int(p2c.dim() == 3), float(near), float(far)
+    a.pixtocam_per_camera, a.near, a.far = int(pixtocams.dim() == 3), float(near), float(far)
     if distortion is not None:
         a.distortion = C.pointer(distortion)
     for name, w in zip(RAY_FIELDS, RAY_FIELD_WIDTHS):
@@ -543,18 +387,11 @@ def train_batch(px0, py0, cam, patch_size, images, pixtocams, camtoworlds, near,
     for name, stack, tail in (("disps", disps, ()), ("normals", normals, (3,)), ("alphas", alphas, ())):
         if stack is None:
             continue
-        stack = f32(stack, name)
-        assert tuple(stack.shape) == (n, H, W) + tail, f"{name}: float32 {(n, H, W) + tail}"
+        setattr(a, "d_" + name, _arg(stack, name, shape=(n, H, W) + tail, exc=AssertionError))
         got[name] = torch.empty(shape + tail, dtype=torch.float32, device=dev)
-        setattr(a, "d_" + name, stack.data_ptr())
         setattr(a, "d_out_" + name, got[name].data_ptr())
     check(lib().refnerf_train_batch(C.byref(a), stream_ptr()))
     return rays, got
-
-
-def _check_t(t, dtype, what):
-    assert torch.is_tensor(t) and t.is_cuda and t.dtype == dtype and t.is_contiguous(), f"{what}: contiguous {dtype} device tensor"
-    return t
 
 
 def mlp_forward(packed, cfg: LevelCfg, means, covs, viewdirs):
@@ -706,11 +543,7 @@ def regularisers_args(weights, acc, clean, noisy, rays, noisy_rays, n, a, thr_en
     dev = acc.device
 
     def p(t, shape, what):
-        if t is None:
-            return None
-        if not (t.is_cuda and t.device == dev and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape):
-            raise ValueError(f"ray regularisers: {what} must be a contiguous float32 tensor of shape {shape} on {dev}")
-        return t.data_ptr()
+        return _arg(t, "ray regularisers: " + what, shape=shape, device=dev, optional=True)
     R = acc.shape[0]
     S = weights.shape[1] if weights is not None else 1
     A = RegularisersArgs()
@@ -769,34 +602,15 @@ def noisy_rays(rotations, distance, fields):
     A = NoisyRaysArgs()
     A.n, A.a = n, a
 
-    def p(t, shape, what):
-        if not (t.is_cuda and t.device == dev and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape):
-            raise ValueError(f"noisy_rays: {what} must be a contiguous float32 tensor of shape {shape} on {dev}")
-        return t.data_ptr()
-    A.d_rotations, A.d_distance = p(rotations, (a, 3, 3), "rotations"), p(distance, (n,), "distance")
+    A.d_rotations = _arg(rotations, "noisy_rays: rotations", shape=(a, 3, 3), device=dev)
+    A.d_distance = _arg(distance, "noisy_rays: distance", shape=(n,), device=dev)
     outs = []
     for name, w, t in zip(RAY_FIELDS, RAY_FIELD_WIDTHS, fields):
-        setattr(A, "d_" + name, p(t, (n, w), name))
+        setattr(A, "d_" + name, _arg(t, "noisy_rays: " + name, shape=(n, w), device=dev))
         outs.append(torch.empty((a * n, w), dtype=torch.float32, device=dev))
         setattr(A, "d_out_" + name, outs[-1].data_ptr())
     check(lib().refnerf_noisy_rays(C.byref(A), stream_ptr()))
     return outs
-
-
-def _checked_ptr(t, shape, dev, what):
-    """data pointer of a contiguous float32 tensor of exactly `shape` on `dev` (None passes through: an absent group)"""
-    if t is None:
-        return None
-    if not (t.is_cuda and t.device == dev and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == tuple(shape)):
-        raise ValueError(f"{what} must be a contiguous float32 tensor of shape {tuple(shape)} on {dev}")
-    return t.data_ptr()
-
-
-def _upstream_ptr(upstream, dev, what):
-    if not (upstream.is_cuda and upstream.device == dev and upstream.dtype == torch.float32 and upstream.is_contiguous() and
-            upstream.numel() == 1):
-        raise ValueError(f"{what}: upstream must be a float32 device tensor of one element")
-    return upstream.data_ptr()
 
 
 def data_terms_args(rgb, gt_rgb, lossmult, penalty, charb_padding, distance_mean=None, disps=None, acc=None, alphas=None,
@@ -812,7 +626,7 @@ def data_terms_args(rgb, gt_rgb, lossmult, penalty, charb_padding, distance_mean
     for name, t, shape in (("rgb", rgb, (R, 3)), ("gt_rgb", gt_rgb, (R, 3)), ("lossmult", lossmult, (R,)),
                            ("distance_mean", distance_mean, (R,)), ("disps", disps, (R,)), ("acc", acc, (R,)),
                            ("alphas", alphas, (R,)), ("normals", normals, (R, 3)), ("normals_gt", normals_gt, (R, 3))):
-        setattr(A, "d_" + name, _checked_ptr(t, shape, dev, "data terms: " + name))
+        setattr(A, "d_" + name, _arg(t, "data terms: " + name, shape=shape, device=dev, optional=True))
     return A
 
 
@@ -828,7 +642,7 @@ def data_terms_forward(A: DataTermsArgs, device):
 def data_terms_backward(A: DataTermsArgs, upstream):
     """refnerf_data_terms_backward: upstream = one device float (multiplier / normaliser x grad_output) -> g_rgb [R,3]."""
     require_device()
-    A.d_upstream = _upstream_ptr(upstream, upstream.device, "data terms")
+    A.d_upstream = _arg(upstream, "data terms: upstream", numel=1)
     g_rgb = torch.empty((max(int(A.R), 1), 3), dtype=torch.float32, device=upstream.device)
     A.d_g_rgb = g_rgb.data_ptr()
     check(lib().refnerf_data_terms_backward(C.byref(A), stream_ptr()))
@@ -843,9 +657,9 @@ def depth_smoothness_args(distance, acc, rgb):
     P, S = int(distance.shape[0]), int(distance.shape[1])
     A = DepthSmoothnessArgs()
     A.P, A.S = P, S
-    A.d_distance = _checked_ptr(distance, (P, S, S), dev, "depth smoothness: distance")
-    A.d_acc = _checked_ptr(acc, (P, S, S), dev, "depth smoothness: acc")
-    A.d_rgb = _checked_ptr(rgb, (P, S, S, 3), dev, "depth smoothness: rgb")
+    A.d_distance = _arg(distance, "depth smoothness: distance", shape=(P, S, S), device=dev, optional=True)
+    A.d_acc = _arg(acc, "depth smoothness: acc", shape=(P, S, S), device=dev, optional=True)
+    A.d_rgb = _arg(rgb, "depth smoothness: rgb", shape=(P, S, S, 3), device=dev, optional=True)
     return A
 
 
@@ -861,21 +675,12 @@ def depth_smoothness_forward(A: DepthSmoothnessArgs, device):
 def depth_smoothness_backward(A: DepthSmoothnessArgs, upstream):
     """refnerf_depth_smoothness_backward: upstream = one device float -> g_distance [P,S,S]."""
     require_device()
-    A.d_upstream = _upstream_ptr(upstream, upstream.device, "depth smoothness")
+    A.d_upstream = _arg(upstream, "depth smoothness: upstream", numel=1)
     P, S = max(int(A.P), 1), max(int(A.S), 1)
     g = torch.empty((P, S, S), dtype=torch.float32, device=upstream.device)
     A.d_g_distance = g.data_ptr()
     check(lib().refnerf_depth_smoothness_backward(C.byref(A), stream_ptr()))
     return g
-
-
-def _ptr32(t):
-    """data pointer of an fp32 device tensor; contiguity is the caller's check (views of a blob are welcome)"""
-    if t is None:
-        return None
-    if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
-        raise ValueError("the optimiser kernels take contiguous float32 device tensors")
-    return C.c_void_p(t.data_ptr())
 
 
 def optim_state_bytes(max_tensors: int) -> int:
@@ -911,8 +716,9 @@ def optim_stats(grad, param, n_seg: int, n_items: int, grad_max_val: float, work
     """refnerf_optim_stats: the four partial sums per work item of one tensor, and its entry `slot` in the state's table."""
     if grad.numel() != param.numel():
         raise ValueError("optim_stats: gradient and parameter differ in size")
-    check(lib().refnerf_optim_stats(_ptr32(grad), _ptr32(param), param.numel(), n_seg, n_items, float(grad_max_val), ptr(workspace),
-                                    workspace.numel(), _ptr32(seg_stats), ptr(state), state.numel(), int(slot), stream_ptr()))
+    g, p, stats = (_arg(t, "optim_stats: " + what, optional=True) for t, what in ((grad, "grad"), (param, "param"), (seg_stats, "seg_stats")))
+    check(lib().refnerf_optim_stats(g, p, param.numel(), n_seg, n_items, float(grad_max_val), ptr(workspace), workspace.numel(), stats,
+                                    ptr(state), state.numel(), int(slot), stream_ptr()))
 
 
 def optim_finalize(state, n_tensors: int, grad_max_norm: float):
@@ -926,15 +732,9 @@ def optim_adam_step(param, grad, exp_avg, exp_avg_sq, cfg: AdamCfg, state):
     for t in (param, exp_avg, exp_avg_sq):
         if t is not None and t.numel() != n:
             raise ValueError("optim_adam_step: tensors differ in size")
-    check(lib().refnerf_optim_adam_step(_ptr32(param), _ptr32(grad), _ptr32(exp_avg), _ptr32(exp_avg_sq), n, C.byref(cfg), ptr(state),
-                                        stream_ptr()))
-
-
-def _rows32(t, shape, what):
-    """data pointer of a contiguous float32 device tensor of `shape` (None for an empty one: the library launches nothing then)"""
-    if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == tuple(shape)):
-        raise ValueError(f"{what} must be a contiguous float32 device tensor of shape {tuple(shape)}")
-    return C.c_void_p(t.data_ptr()) if t.numel() else None
+    ptrs = [_arg(t, "optim_adam_step: " + what, optional=True)
+            for t, what in ((param, "param"), (grad, "grad"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq"))]
+    check(lib().refnerf_optim_adam_step(*ptrs, n, C.byref(cfg), ptr(state), stream_ptr()))
 
 
 def max_dilate_weights(t, w, dilation, lo, hi):
@@ -947,7 +747,8 @@ def max_dilate_weights(t, w, dilation, lo, hi):
     R, M = w.shape
     sd = torch.empty((R, max(3 * M - 1, 0)), dtype=torch.float32, device=t.device)
     wd = torch.empty((R, max(3 * M - 2, 0)), dtype=torch.float32, device=t.device)
-    check(lib().refnerf_max_dilate_weights(_rows32(t, (R, M + 1), "max_dilate_weights: t"), _rows32(w, (R, M), "max_dilate_weights: w"),
+    check(lib().refnerf_max_dilate_weights(_arg(t, "max_dilate_weights: t", shape=(R, M + 1), empty_null=True),
+                                           _arg(w, "max_dilate_weights: w", shape=(R, M), empty_null=True),
                                            R, M, float(dilation), float(lo), float(hi), ptr(sd) if sd.numel() else None,
                                            ptr(wd) if wd.numel() else None, stream_ptr()))
     return sd, wd
@@ -957,8 +758,8 @@ def _interlevel_args(t, w, t_env, w_env):
     if w.dim() != 2 or w_env.dim() != 2 or w.shape[0] != w_env.shape[0]:
         raise ValueError("interlevel loss: w [R, N] and w_env [R, Np]")
     (R, N), Np = w.shape, w_env.shape[1]
-    return (_rows32(t, (R, N + 1), "interlevel loss: t"), _rows32(w, (R, N), "interlevel loss: w"),
-            _rows32(t_env, (R, Np + 1), "interlevel loss: t_env"), _rows32(w_env, (R, Np), "interlevel loss: w_env"), R, N, Np)
+    shapes = (("t", t, (R, N + 1)), ("w", w, (R, N)), ("t_env", t_env, (R, Np + 1)), ("w_env", w_env, (R, Np)))
+    return tuple(_arg(x, "interlevel loss: " + what, shape=shape, empty_null=True) for what, x, shape in shapes) + (R, N, Np)
 
 
 def interlevel_forward(t, w, t_env, w_env):
@@ -977,7 +778,7 @@ def interlevel_backward(t, w, t_env, w_env, upstream):
     require_device()
     args = _interlevel_args(t, w, t_env, w_env)
     g = torch.empty((args[4], args[6]), dtype=torch.float32, device=w.device)
-    check(lib().refnerf_interlevel_backward(*args, _rows32(upstream.reshape(1), (1,), "interlevel loss: upstream"),
+    check(lib().refnerf_interlevel_backward(*args, _arg(upstream.reshape(1), "interlevel loss: upstream", shape=(1,), empty_null=True),
                                             ptr(g) if g.numel() else None, stream_ptr()))
     return g
 
@@ -1243,10 +1044,7 @@ def set_timing(enable: bool):
     lib().refnerf_set_timing(int(enable))
 
 
-TIMER_FORWARD, TIMER_BACKWARD, TIMER_WGRAD, TIMER_IMAGE, TIMER_DATASET = 0, 1, 2, 3, 4
-
-
-def get_timing(family: int = TIMER_FORWARD):
+def get_timing(family: int = TIMER_FORWARD):       # REFNERF_TIMER_*
     """(total ms, launches) of the kernels of one family launched since set_timing(True)."""
     ms, n = C.c_double(0), C.c_int64(0)
     check(lib().refnerf_get_timing_family(family, C.byref(ms), C.byref(n)))

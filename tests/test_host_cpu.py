@@ -26,6 +26,8 @@ def test_library_exports_every_declared_symbol():
     """The C-ABI library loads and exports exactly what include/refnerf_hip.h declares."""
     hdr = open(os.path.join(ROOT, "include", "refnerf_hip.h")).read()
     names = set(re.findall(r"\b(refnerf_[a-z_0-9]+)\s*\(", hdr))
+    from refnerf_pl_amd import _abi
+    assert names == set(_abi.prototypes)            # the binding's parser (which _hip.lib() binds from) drops no declaration
     assert {"refnerf_level_forward", "refnerf_pack_weights", "refnerf_sample_intervals",
             "refnerf_integrated_pos_enc", "refnerf_integrated_dir_enc"} <= names
     lib = _hip.lib()
