@@ -124,6 +124,16 @@ def resample_logits(t, w, anneal=1.0, padding=0.01):
     return out
 
 
+def resample_cdf(w_logits):
+    """w_logits [R,M] -> the CDF at the knots [R,M+1] that sample_intervals inverts (rn_resample_cdf)."""
+    w_logits, _ = _f(w_logits)
+    R, M = w_logits.shape
+    cw = np.empty((R, M + 1), _NP)
+    for r in range(R):
+        lib().rn_resample_cdf(w_logits[r].ctypes.data_as(_FP), C.c_int(M), cw[r].ctypes.data_as(_FP))
+    return cw
+
+
 def sample_intervals(t, w_logits, n, smin=0.0, smax=1.0):
     """t [R,M+1], w_logits [R,M] -> sdist [R,n+1], bin_idx [R,n]."""
     t, _ = _f(t)

@@ -110,12 +110,9 @@ static float nan_to_num0(float x) { /* torch.nan_to_num(x, 0) */
 }
 static float clip01(float x) { return fminf(fmaxf(x, 0.0f), 1.0f); }
 
-/* stepfun.py:209-258 -> sample (168-206) -> invert_cdf (157-165)
- * -> integrate_weights (134-154) -> math.sorted_interp (math.py:88-111). */
-void rn_sample_intervals(const float *t, const float *w_logits, int M, int N,
-                         float smin, float smax, float *sdist, int32_t *bin_idx) {
-  float *p = (float *)malloc(sizeof(float) * (size_t)(M + (M + 1) + N + N));
-  float *cw = p + M, *u = cw + (M + 1), *c = u + N;
+/* invert_cdf's first half (stepfun.py:160-161): softmax, then integrate_weights (134-154) -> cw[M+1], the CDF at the knots */
+void rn_resample_cdf(const float *w_logits, int M, float *cw) {
+  float *p = (float *)malloc(sizeof(float) * (size_t)M);
   /* softmax (stepfun.py:160); exp through the shared bit-reproducible
    * rn_det_expf so that the HIP path can match the CDF bit for bit. */
   float mx = -INFINITY;
@@ -132,6 +129,16 @@ void rn_sample_intervals(const float *t, const float *w_logits, int M, int N,
     cw[i + 1] = fminf(1.0f, (float)acc);
   }
   cw[M] = 1.0f;
+  free(p);
+}
+
+/* stepfun.py:209-258 -> sample (168-206) -> invert_cdf (157-165)
+ * -> integrate_weights (134-154) -> math.sorted_interp (math.py:88-111). */
+void rn_sample_intervals(const float *t, const float *w_logits, int M, int N,
+                         float smin, float smax, float *sdist, int32_t *bin_idx) {
+  float *cw = (float *)malloc(sizeof(float) * (size_t)((M + 1) + N + N));
+  float *u = cw + (M + 1), *c = u + N;
+  rn_resample_cdf(w_logits, M, cw);
   rn_linspace_u(N, u);
   /* sorted_interp: for each u find the bracketing CDF knots by value. */
   for (int k = 0; k < N; ++k) {
@@ -152,7 +159,7 @@ void rn_sample_intervals(const float *t, const float *w_logits, int M, int N,
   for (int k = 0; k < N - 1; ++k) sdist[k + 1] = (c[k + 1] + c[k]) / 2.0f;
   sdist[0] = fmaxf(smin, 2.0f * c[0] - sdist[1]);
   sdist[N] = fminf(smax, 2.0f * c[N - 1] - sdist[N - 1]);
-  free(p);
+  free(cw);
 }
 
 /* coord.py:96-98 (fn=None): t = s*far + (1-s)*near */

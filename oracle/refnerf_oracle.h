@@ -126,6 +126,9 @@ void rn_linspace_u(int n, float *u);
 void rn_sample_intervals(const float *t, const float *w_logits, int M, int N,
                          float smin, float smax, float *sdist, int32_t *bin_idx);
 
+/* ... its CDF alone (stepfun.py:160-161, 134-154): w_logits[M] -> cw[M+1], cw[0] = 0, cw[M] = 1. */
+void rn_resample_cdf(const float *w_logits, int M, float *cw);
+
 /* models.py:200-203: logits from (sdist, weights). */
 void rn_resample_logits(const float *t, const float *w, int M, float anneal,
                         float padding, float *logits);

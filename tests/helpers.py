@@ -113,3 +113,40 @@ RAYDIST_CODE = {"": 0, "piecewise": 1, "reciprocal": 2, "log": 3, "exp": 4, "sqr
 def raydist_kw(g):
     """level-cfg kwargs of a raydist fixture"""
     return dict(raydist=RAYDIST_CODE[str(g["raydist_fn"])], disable_integration=int(g["disable_integration"]))
+
+
+# ---- adversarial step functions of the sample-index contract (tests/golden/make_golden_sampler_adversarial.py) ----------
+def cdf_delta(M):
+    """How far two fp32 evaluations of one M-bin CDF can lie apart at a knot: M 2^-24 for a sequential sum of the softmax,
+    (M / 64 + 6) 2^-24 for a wave-parallel tree over the same terms, 3 2^-24 for the divisions and the final rounding."""
+    return (M + M / 64 + 9) * 2.0 ** -24
+
+
+def adversarial_cases(kind, shape=None):
+    """The cases of tests/golden/sampler_adversarial.npz of one kind ('stage': logits given; 'level': weights, anneal and
+    resample_padding given), optionally of one (M, N): dicts with id, family, M, N, t [5, M + 1], smin, smax, then `logits`
+    [5, M] or `w` [5, M] + anneal + padding, and the reference's idx [5, N], sdist [5, N + 1] and the mask [5, N] of the
+    quantiles within cdf_delta(M) of one of its CDF knots."""
+    g = load_golden("sampler_adversarial")
+    out = []
+    for s, (M, N) in enumerate(g[kind + "_shapes"]):
+        M, N = int(M), int(N)
+        if shape is not None and (M, N) != tuple(shape):
+            continue
+        pre = f"{kind}_s{s}_"
+        ref = {k: g[pre + k] for k in ("idx", "sdist", "mask")}
+        if kind == "stage":
+            for f, fam in enumerate(g["stage_families"]):
+                out.append(dict(id=f"{fam}-{M}x{N}", family=str(fam), M=M, N=N, t=g[pre + "t"][f], logits=g[pre + "logits"][f],
+                                smin=float(g["stage_domain"][f, 0]), smax=float(g["stage_domain"][f, 1]),
+                                idx=ref["idx"][f].astype(np.int32), sdist=ref["sdist"][f], mask=ref["mask"][f]))
+            continue
+        for d in range(2):
+            for f, fam in enumerate(g["level_families"]):
+                for p, (anneal, padding) in enumerate(g["level_pairs"]):
+                    if not g["level_legal"][f, p]:
+                        continue
+                    out.append(dict(id=f"{fam}{'-dup' if d else ''}-a{anneal:g}-p{padding:g}-{M}x{N}", family=str(fam), M=M, N=N,
+                                    t=g[pre + "t"][d], w=g[pre + "w"][d, f], anneal=float(anneal), padding=float(padding), smin=0.0, smax=1.0,
+                                    idx=ref["idx"][d, f, p].astype(np.int32), sdist=ref["sdist"][d, f, p], mask=ref["mask"][d, f, p]))
+    return out
