@@ -37,239 +37,11 @@
 #include "refnerf_proposal.h"
 #include "refnerf_image.h"
 #include "refnerf_vis.h"
-#include "refnerf_pack_common.h"
 #include "refnerf_sq_host.h"
 #include "refnerf_sq_layout.h"
+#include "refnerf_pack.h"
 
 namespace rn {
-
-/* ------------------------------------------------------------------ */
-/* weight packing                                                     */
-/* ------------------------------------------------------------------ */
-
-
-/* element e of an fp32 A image -> (k-step, row block, lane): [step][lane][ob], eight-block ops [step][q][lane][4] with ob = 4 q + e % 4 */
-__device__ __forceinline__ void a_decode(int e, int stride, int &step, int &ob, int &lane) {
-  step = e / (stride * 64);
-  if (stride == 8) { const int rem = e % 512; ob = (rem >> 8) * 4 + (rem & 3); lane = (rem & 255) >> 2; }
-  else { ob = e % stride; lane = (e / stride) % 64; }
-}
-
-/* ---- the 16-bit images of the chain GEMMs: [k-step][ob][lane][8], element e of lane (h = lane / 32, n = lane % 32) ---- */
-/* accumulator row that feeds slot (h, e) of 16-wide k-step st */
-__device__ __forceinline__ int kslot16(int st, int h, int e) {
-  const int r = 8 * (st & 1) + e;
-  return 32 * (st >> 1) + (r & 3) + 8 * (r >> 2) + 4 * h;
-}
-/* transposed op t (refnerf_layout.h: bt_off / ht_off): W[o = k slot][in_row = 32 ob + n] */
-__device__ __forceinline__ float top16_value(const float *__restrict__ P, int t, int st, int ob, int lane, int e) {
-  const Op o = PACKED.top[t];
-  const int h = lane >> 5, in_row = ob * 32 + (lane & 31);
-  if (ob >= o.nob) return 0.0f;
-  if (t == TOP_HEADS) {
-    const int hr = 16 * st + 8 * h + e;                      /* head row feeding this k slot */
-    return (hr < HROWS) ? canon_w(P, OP_HEADS, hr, in_row) : 0.0f;
-  }
-  const TopSrc src = PACKED.top_src[t];
-  const int n_rows = (o.nob == 8) ? WIDTH : (o.nob == 3 ? IPE_DIM : DIR_IN);   /* rows beyond are padding */
-  return (in_row < n_rows) ? canon_w(P, src.fwd_op, kslot16(st, h, e), src.col0 + in_row) : 0.0f;
-}
-/* forward op fo (bf_off / hf_off): W[row = 32 ob + n][k], register steps in k-slot order, then the LDS steps in plain order */
-__device__ __forceinline__ float fwd16_value(const float *__restrict__ P, int fo, int st, int ob, int lane, int e) {
-  const int rst = bf_reg_steps(fo);
-  const int h = lane >> 5, row = ob * 32 + (lane & 31);
-  if (ob >= PACKED.op[fo].nob) return 0.0f;
-  if (st < rst) return canon_w(P, fo, row, kslot16(st, h, e));
-  const int kl = 16 * (st - rst) + 8 * h + e;
-  const int valid_k = (fo == 0 || fo == 5) ? IPE_DIM : DIR_IN;
-  return (kl < valid_k) ? canon_w(P, fo, row, (rst ? WIDTH : 0) + kl) : 0.0f;
-}
-/* the two stores: bf16, or the split-f16 pair -- per k-step [hi | lo], the v - hi residual 4096 halves behind its hi half */
-__device__ __forceinline__ void store16(__bf16 *dst, int idx, float v) { dst[idx] = (__bf16)v; }
-__device__ __forceinline__ void store16(_Float16 *dst, int idx, float v) {
-  const _Float16 hi = (_Float16)v;
-  const size_t base = (size_t)(idx >> 12) * (2 * 4096) + (idx & 4095);
-  dst[base] = hi;
-  dst[base + 4096] = (_Float16)(v - (float)hi);
-}
-/* one image of `steps` k-steps, value(st, ob, lane, e), by the whole x-grid */
-template <typename E, typename F>
-__device__ __forceinline__ void pack_image16(E *dst, int steps, F &&value) {
-  for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < steps * 4096; idx += gridDim.x * blockDim.x)
-    store16(dst, idx, value(idx >> 12, (idx >> 9) & 7, (idx >> 3) & 63, idx & 7));
-}
-
-__global__ void pack_weights_f32(const float *__restrict__ P, float *__restrict__ out) {
-  int op = blockIdx.y;
-  if (op < NUM_OPS) {
-    const Op o = PACKED.op[op];
-    int n_a = (o.reg_steps + o.lds_steps) * 64 * o.stride;
-    int n_b = o.nob * 32;
-    for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < n_a + n_b; e += gridDim.x * blockDim.x) {
-      if (e < n_a) {
-        int step, ob, lane;
-        a_decode(e, o.stride, step, ob, lane);
-        int h = lane >> 5, row = ob * 32 + (lane & 31);
-        float v = 0.0f;
-        if (ob < o.nob) {
-          if (step < o.reg_steps) {
-            int kb = step >> 4, r = step & 15;
-            int k = 32 * kb + (r & 3) + 8 * (r >> 2) + 4 * h;
-            v = canon_w(P, op, row, k);
-          } else {
-            int kl = 2 * (step - o.reg_steps) + h;
-            int k = (o.reg_steps ? WIDTH : 0) + kl;
-            int valid_k = (op == 0 || op == 5) ? IPE_DIM : DIR_IN;
-            v = (kl < valid_k) ? canon_w(P, op, row, k) : 0.0f;
-          }
-        }
-        out[o.a_off + e] = v;
-      } else {
-        int b = e - n_a;
-        int reg = b & 15, h = (b >> 4) & 1, ob = b >> 5;
-        int row = ob * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * h;
-        out[o.b_off + b] = canon_b(P, op, row);
-      }
-    }
-  } else if (op < NUM_OPS + NUM_TOPS) {
-    /* transposed ops: A[step][lane][ob] = W[o = k slot][in_row] (see refnerf_layout.h) */
-    const int t = op - NUM_OPS;
-    const Op o = PACKED.top[t];
-    const TopSrc src = PACKED.top_src[t];
-    int n_a = (o.reg_steps + o.lds_steps) * 64 * o.stride;
-    for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < n_a; e += gridDim.x * blockDim.x) {
-      int step, ob, lane;
-      a_decode(e, o.stride, step, ob, lane);
-      int h = lane >> 5, in_row = ob * 32 + (lane & 31);
-      float v = 0.0f;
-      if (ob < o.nob) {
-        if (t == TOP_HEADS) {
-          int hr = 2 * step + h;                               /* head row feeding this k slot */
-          v = (hr < HROWS) ? canon_w(P, OP_HEADS, hr, in_row) : 0.0f;
-        } else {
-          int kb = step >> 4, r = step & 15;
-          int oo = 32 * kb + (r & 3) + 8 * (r >> 2) + 4 * h;   /* output feature feeding this k slot */
-          v = canon_w(P, src.fwd_op, oo, src.col0 + in_row);
-        }
-      }
-      out[o.a_off + e] = v;
-    }
-  } else if (op < 3 * NUM_OPS + 3 * NUM_TOPS) {
-    /* the 16-bit images, in blob order: bf16 transposed (bt_off: the bf16-chain backward), bf16 forward (bf_off: the bf16-chain
-     * training forward), split-f16 transposed (ht_off), split-f16 forward (hf_off) */
-    const int j = op - NUM_OPS - NUM_TOPS, half = NUM_TOPS + NUM_OPS;
-    const bool split = j >= half;
-    const int i = split ? j - half : j;                     /* transposed op i, or forward op i - NUM_TOPS */
-    if (i < NUM_TOPS) {
-      const int t = i, steps = (t == TOP_HEADS) ? BT_HEADS_STEPS : BT_CHAIN_STEPS;
-      auto value = [&](int st, int ob, int lane, int e) { return top16_value(P, t, st, ob, lane, e); };
-      if (split) pack_image16(reinterpret_cast<_Float16 *>(out + PACKED.ht_off[t]), steps, value);
-      else pack_image16(reinterpret_cast<__bf16 *>(out + PACKED.bt_off[t]), steps, value);
-    } else {
-      const int fo = i - NUM_TOPS, steps = bf_reg_steps(fo) + bf_lds_steps(fo);
-      auto value = [&](int st, int ob, int lane, int e) { return fwd16_value(P, fo, st, ob, lane, e); };
-      if (split) pack_image16(reinterpret_cast<_Float16 *>(out + PACKED.hf_off[fo]), steps, value);
-      else pack_image16(reinterpret_cast<__bf16 *>(out + PACKED.bf_off[fo]), steps, value);
-    }
-  } else {
-    /* WD / WRGB: raw_density.weight and rgb_layer.weight rows in accumulator layout [ob][h][16] */
-    for (int b = blockIdx.x * blockDim.x + threadIdx.x; b < 4 * 8 * 32; b += gridDim.x * blockDim.x) {
-      int reg = b & 15, h = (b >> 4) & 1, ob = (b >> 5) & 7, which = b >> 8;
-      int k = ob * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * h;
-      if (which == 0) out[PACKED.wd_off + (b & 255)] = P[CANON.density_w + k];
-      else out[PACKED.wrgb_off + (which - 1) * 256 + (b & 255)] = P[CANON.rgb_w + (which - 1) * WIDTH + k];
-    }
-  }
-}
-
-/* Tail of the fp32 image for a general IPE basis (refnerf_layout.h): the basis directions, the forward group ops
- * (op 0's LDS-step format: A[step][q][lane][4] = W[32 ob + lane % 32][k = 2 step + h]) and their transposes (TOP_SP0's
- * format: A[step][lane][4] = W[o(step, h)][in_row = 32 ob + lane % 32], ob < 3) of the tail weights. */
-__global__ void pack_weights_ext(const float *__restrict__ P, const float *__restrict__ basis, int groups, float *__restrict__ out) {
-  const int e0 = blockIdx.x * blockDim.x + threadIdx.x, stride = gridDim.x * blockDim.x;
-  const int which = blockIdx.y;              /* 0: basis, then 12 blocks each: fp32 forward, fp32 transposed, split forward, split transposed */
-  if (which == 0) {
-    for (int e = e0; e < 64; e += stride) out[PEXT_BASIS + e] = (e < 9 * groups) ? basis[e] : 0.0f;
-    return;
-  }
-  const int idx = (which - 1) % (2 * EXT_GROUPS), L = idx / EXT_GROUPS, g = idx % EXT_GROUPS + 1;
-  const float *W = P + ext_w_off(L, g);      /* [256 rows, pitch EXT_K][96] */
-  const bool live = g < groups;
-  const int kind = (which - 1) / (2 * EXT_GROUPS);   /* 0: fp32 forward, 1: fp32 transposed, 2: split forward, 3: split transposed */
-  if (kind == 0) {
-    float *dst = out + pext_fwd_off(L, g);
-    for (int e = e0; e < PEXT_FWD_FLOATS; e += stride) {
-      const int step = e >> 9, rem = e & 511, ob = (rem >> 8) * 4 + (rem & 3), lane = (rem & 255) >> 2;
-      const int h = lane >> 5, row = ob * 32 + (lane & 31), k = 2 * step + h;
-      dst[e] = live ? W[row * EXT_K + k] : 0.0f;
-    }
-  } else if (kind == 1) {
-    float *dst = out + pext_t_off(L, g);
-    for (int e = e0; e < PEXT_T_FLOATS; e += stride) {
-      const int ob = e & 3, lane = (e >> 2) & 63, step = e >> 8;
-      const int h = lane >> 5, in_row = ob * 32 + (lane & 31), kb = step >> 4, r = step & 15;
-      const int oo = 32 * kb + (r & 3) + 8 * (r >> 2) + 4 * h;
-      dst[e] = (live && ob < 3) ? W[oo * EXT_K + in_row] : 0.0f;
-    }
-  } else {
-    /* split copies: the [k-step][hi | lo][ob][lane][8] layout of ht_off / hf_off */
-    const bool fwd = kind == 2;
-    _Float16 *dst = reinterpret_cast<_Float16 *>(out + (fwd ? pext_hf_off(L, g) : pext_ht_off(L, g)));
-    pack_image16(dst, fwd ? BF_IPE_STEPS : BT_CHAIN_STEPS, [&](int st, int ob, int lane, int e) {
-      const int h = lane >> 5, r32 = ob * 32 + (lane & 31);
-      if (!live) return 0.0f;
-      if (fwd) return W[r32 * EXT_K + 16 * st + 8 * h + e];   /* plain order over the fp32 X tile (bf_off's LDS steps) */
-      return ob < 3 ? W[kslot16(st, h, e) * EXT_K + r32] : 0.0f;
-    });
-  }
-}
-
-/* bf16 image: one block per (op, ob) slice, uniform 17 KB chunks in execution
- * order; see refnerf_layout.h. */
-template <typename E>   /* E = __bf16 (REFNERF_PREC_BF16) or _Float16 (REFNERF_PREC_F16): same image layout */
-__global__ void pack_weights_16(const float *__restrict__ P, char *__restrict__ out) {
-  const int op = blockIdx.y, ob = blockIdx.x;
-  const BfOp o = BFPACKED.op[op];
-  if (ob >= o.nob) return;
-  const int base = (o.nchunk == 2) ? WIDTH : 0;     /* canonical column of the first non-register input */
-  for (int j = 0; j < o.nchunk; ++j)
-    fill_chunk_plain<E>(P, out + (size_t)(o.chunk0 + ob * o.nchunk + j) * BF_CHUNK_BYTES, op, ob, o.kind[j], j == 0, base);
-}
-
-/* ... and a plain BNLDS chunk whose eight bottleneck k-steps follow the merged-run order of that section */
-__device__ void fill_chunk_bnlds_sq(const float *__restrict__ P, char *__restrict__ chunk, int op, int ob, bool first, int base) {
-  fill_chunk_plain<_Float16>(P, chunk, op, ob, BF_BNLDS, first, base);
-  __syncthreads();
-  for (int idx = threadIdx.x; idx < 8 * 512; idx += blockDim.x) {
-    const int e = idx & 7, lane = (idx >> 3) & 63, t = idx >> 9;
-    const int h = lane >> 5, row = ob * 32 + (lane & 31);
-    const int feat = 32 * (t >> 1) + 16 * (e >> 2) + 8 * h + 4 * (t & 1) + (e & 3);
-    reinterpret_cast<_Float16 *>(chunk + 1024)[idx] = (_Float16)canon_w(P, op, row, base + feat);
-  }
-}
-__global__ void pack_weights_split(const float *__restrict__ P, char *__restrict__ out) {
-  const int op = blockIdx.y, ob = blockIdx.x;
-  const int nob = (op == OP_HEADS) ? 5 : (op == OP_RGB ? 1 : 8);
-  if (ob >= nob) return;
-  int c = SPPACKED.chunk0[op];
-  for (int o2 = 0; o2 < ob; ++o2) c += sp_slice_chunks(op, o2);
-  char *chunk = out + (size_t)c * BF_CHUNK_BYTES;
-  if (op > OP_HEADS) {
-    const BfOp o = BFPACKED.op[op];
-    const int base = (o.nchunk == 2) ? WIDTH : 0;
-    for (int j = 0; j < o.nchunk; ++j) {
-      if (o.kind[j] == BF_BNLDS) fill_chunk_bnlds_sq(P, chunk + (size_t)j * BF_CHUNK_BYTES, op, ob, j == 0, base);
-      else fill_chunk_plain<_Float16>(P, chunk + (size_t)j * BF_CHUNK_BYTES, op, ob, o.kind[j], j == 0, base);
-    }
-    return;
-  }
-  const int n = sp_slice_chunks(op, ob);
-  if (op == OP_HEADS) { fill_chunk_sq(P, chunk, op, ob, ob < 4 ? SQ_BN : SQ_SC, true, 0); return; }
-  for (int j = 0; j < n; ++j) {
-    const int kind = (op == 0 || j == 2) ? SQ_X : (j == 0 ? SQ_A : SQ_B);
-    fill_chunk_sq(P, chunk + (size_t)j * BF_CHUNK_BYTES, op, ob, kind, j == 0, op == 5 ? WIDTH : 0);
-  }
-}
 
 /* ------------------------------------------------------------------ */
 /* stage kernels                                                      */
@@ -562,7 +334,7 @@ size_t refnerf_packed_weights_bytes(int precision) {
   if (precision == REFNERF_PREC_F32) return (size_t)rn::PACKED.total * sizeof(float);
   if (precision == REFNERF_PREC_BF16 || precision == REFNERF_PREC_F16) return ((size_t)rn::BFPACKED.chunks_per_pass + 2) * rn::BF_CHUNK_BYTES;
   if (precision == REFNERF_PREC_F16X2) return ((size_t)rn::SPPACKED.total_chunks + 2) * rn::BF_CHUNK_BYTES;
-  if (precision == REFNERF_IMAGE_F16X2_TRAIN) return rnsq::image_bytes();
+  if (precision == REFNERF_IMAGE_F16X2_TRAIN) return rn::TR_IMAGE_BYTES;
   return 0;
 }
 
@@ -629,7 +401,9 @@ int refnerf_pack_weights(const float *d_params, void *d_packed, int precision, v
     dim3 grid(8, rn::NUM_OPS);
     hipLaunchKernelGGL(rn::pack_weights_split, grid, dim3(256), 0, (hipStream_t)stream, d_params, (char *)d_packed);
   } else if (precision == REFNERF_IMAGE_F16X2_TRAIN) {
-    return rnsq::pack(d_params, d_packed, (hipStream_t)stream);
+    hipLaunchKernelGGL(rn::pack_train_chunks, dim3(rn::TR_CHUNKS), dim3(256), 0, (hipStream_t)stream, d_params, (char *)d_packed);
+    hipLaunchKernelGGL(rn::pack_train_consts, dim3(rn::TRG_N), dim3(1024), 0, (hipStream_t)stream, d_params,
+                       (float *)((char *)d_packed + rn::TR_CONST_OFF));
   } else {
     return fail(REFNERF_EINVAL, "refnerf_pack_weights: unknown precision%s");
   }

@@ -342,6 +342,8 @@ constexpr int sp_slice_chunks(int op, int ob) {
   if (op == OP_HEADS) return 1;
   return (op == 14) ? 2 : 1;
 }
+/* chunk j of a spatial slice (ops 0..7): sp0 [SQ_X]; sp5 [SQ_A][SQ_B][SQ_X]; else [SQ_A][SQ_B] */
+constexpr int sq_sp_kind(int op, int j) { return (op == 0 || j == 2) ? SQ_X : (j == 0 ? SQ_A : SQ_B); }
 constexpr SpPacked make_sp_packed() {
   SpPacked P{};
   int c = 0;
@@ -360,5 +362,27 @@ static_assert(SPPACKED.sp_chunks == 133 && SPPACKED.total_chunks == 206, "split 
 
 /* head rows inside op 8 (5 blocks of 32): 0..127 bottleneck, then */
 constexpr int HROW_DENSITY = 128, HROW_GRAD = 129, HROW_ROUGH = 132, HROW_DIFFUSE = 133, HROW_TINT = 136, HROWS = 139;
+
+/* ---------------- index maps of the operand layouts above, each written once (the packers: refnerf_pack.h) ---------------- */
+/* 32x32 shapes (32x32x2_f32, 32x32x16): row of accumulator register `reg` in lane half h of the 32-row block that starts at row0 */
+constexpr int acc_row(int reg, int h, int row0 = 0) { return row0 + (reg & 3) + 8 * (reg >> 2) + 4 * h; }
+/* 32x32x2_f32: accumulator row (over the whole layer) that feeds lane half h in K=2 register step `step` */
+constexpr int kslot2(int step, int h) { return acc_row(step & 15, h, 32 * (step >> 4)); }
+/* 32x32x16 over an fp32 LDS tile: plain position k' of element e of lane half h in k-step st */
+constexpr int klds16(int st, int h, int e) { return 16 * st + 8 * h + e; }
+/* 32x32x16: accumulator row (over the whole layer) that feeds element e of lane half h in 16-wide k-step st */
+constexpr int kslot16(int st, int h, int e) { return acc_row(8 * (st & 1) + e, h, 32 * (st >> 1)); }
+/* 16x16x32: k-column of element e of k-block bk (= lane / 16) in k-step st */
+constexpr int kcol_sq(int st, int bk, int e) { return 32 * st + 16 * (e >> 2) + 4 * bk + (e & 3); }
+/* 32x32x16 over the dir encodings in LDS: position k' of [Re x36 | n.v | 0 0 0 | Im x36 | 0 0 0 0] -> column of the canonical
+ * dir input [bottleneck 128 | IDE 72 | n.v], or -1 for padding */
+constexpr int dir_lds_col(int kp) {
+  return kp < IDE_TERMS ? BNECK + kp : (kp == IDE_TERMS ? BNECK + IDE_DIM : ((kp >= 40 && kp < 40 + IDE_TERMS) ? BNECK + IDE_TERMS + (kp - 40) : -1));
+}
+/* 16x16x32_f16 / 32x32x16_f16 on split operands: half `part` of w = hi + lo, hi = fl16(w), lo = fl16(w - hi) */
+constexpr _Float16 f16_part(float v, int part) {
+  const _Float16 hi = (_Float16)v;
+  return part ? (_Float16)(v - (float)hi) : hi;
+}
 
 }  // namespace rn

@@ -1,6 +1,6 @@
 /*
  * refnerf_sq_host.h -- host-side seam between the two translation units of librefnerf_hip.so:
- * refnerf_hip.hip (C ABI, every kernel of rounds 1-4) and refnerf_sq_train.hip (the round-5 training kernels of the
+ * refnerf_hip.hip (C ABI, every kernel of rounds 1-4, every weight packer: refnerf_pack.h) and refnerf_sq_train.hip (the round-5 training kernels of the
  * parity-grade 16-bit mode: refnerf_sq_layout.h).  Internal: nothing here is part of include/refnerf_hip.h.
  */
 #pragma once
@@ -19,8 +19,6 @@ int lds_pad();
 }  // namespace rnh
 
 namespace rnsq {  /* defined in refnerf_sq_train.hip */
-size_t image_bytes();
-int pack(const float *d_params, void *d_packed, hipStream_t st);
 /* the training forward of one level (REFNERF_PREC_F16X2, built-in basis); d_act: REFNERF_ACT_SQ */
 int forward(const void *d_packed, const refnerf_level_cfg *cfg, const refnerf_rays *rays, int R, const float *d_sdist_in,
             const float *d_weights_in, const refnerf_level_out *out, const refnerf_level_out_extra *extra, float *d_act, hipStream_t st);

@@ -27,7 +27,7 @@ namespace rn {
  * FORWARD stream of a pass = [run section] x 2 (16 samples per wave each) + [directional section] (32 samples per wave):
  *   run section  : spatial ops 0..7 exactly as the eval image (SQ_X / SQ_A / SQ_B chunks, 128 chunks)
  *                  heads: 4 bottleneck slices as [SQ_A SQ_B] (hi + lo weights) + the scalar block [SQ_SC]            9
- *                  VJP  : transposed spatial layers 7..1 (8 slices x [SQ_A SQ_B]); behind layer 5 the 96 IPE rows of layer 5
+ *                  VJP  : transposed spatial layers 7..1 (8 slices x [SQ_A SQ_B]); in front of layer 5 the 96 IPE rows of layer 5
  *                         (3 slices), behind layer 1 those of layer 0 (3 slices)                                  124
  *   directional  : ops 9..16 + rgb as plain f16 chunks of refnerf_layout.h, every chunk twice: [hi][lo]              146
  * BACKWARD stream of a pass (32 samples per wave, two products): plain chunks [hi][lo] of the transposed ops
@@ -57,6 +57,103 @@ constexpr size_t TR_IMAGE_BYTES = TR_CONST_OFF + (size_t)TRC_FLOATS * 4;
  * so a sample's deltas can be rescaled BEFORE the contraction without ever leaving the range of an IEEE half */
 enum { TRG_SP = 0 /* + layer 1..7 */, TRG_SP5_IPE = 8, TRG_SP0 = 9, TRG_VD = 10 /* + layer 1..7 */, TRG_VD5_DIN = 18, TRG_VD0 = 19,
        TRG_HEADS = 20, TRG_RGB = 21, TRG_WD = 22, TRG_N = 23 };
+/* what G[g] sums: `rows` output rows of forward op `op`, max over its input columns col0 .. col0 + ncol (op < 0: slot unused) */
+struct TrG { short op, rows, col0, ncol; };
+struct TrGTable { TrG g[TRG_N]; };
+constexpr TrGTable make_trg_table() {
+  TrGTable t{};
+  for (int g = 0; g < TRG_N; ++g) t.g[g] = TrG{-1, WIDTH, 0, WIDTH};
+  for (int l = 1; l <= 7; ++l) { t.g[TRG_SP + l].op = (short)l; t.g[TRG_VD + l].op = (short)(9 + l); }
+  t.g[TRG_SP5_IPE] = TrG{5, WIDTH, WIDTH, IPE_DIM};
+  t.g[TRG_SP0] = TrG{0, WIDTH, 0, IPE_DIM};
+  t.g[TRG_VD5_DIN] = TrG{14, WIDTH, WIDTH, DIR_IN};
+  t.g[TRG_VD0] = TrG{9, WIDTH, 0, DIR_IN};
+  t.g[TRG_HEADS] = TrG{OP_HEADS, HROWS, 0, WIDTH};
+  t.g[TRG_RGB] = TrG{OP_RGB, 3, 0, WIDTH};
+  t.g[TRG_WD] = TrG{OP_HEADS, 1, 0, WIDTH};       /* the one row HROW_DENSITY */
+  return t;
+}
+constexpr TrGTable TRG_TABLE = make_trg_table();
+
+/* The chunk order above as a table: entry c says how chunk c of the image is filled (refnerf_pack.h).
+ *   TRF_SQ      forward 16x16x32 chunk of `kind` SQ_*: slice ob of op, input columns from `col`; `first`: it carries the bias
+ *   TRF_SQT     its transpose (the VJP): rows col + 32 ob .. of op's inputs, k-steps of kind SQ_A / SQ_B
+ *   TRF_PLAIN   forward plain chunk of `kind` BF_*, half `part` of every weight; LDS-fed columns from `col`
+ *   TRF_PLAIN_T its transpose (the backward): rows col + 32 ob .. of op's inputs, half `part` */
+enum { TRF_SQ = 0, TRF_SQT = 1, TRF_PLAIN = 2, TRF_PLAIN_T = 3 };
+struct TrChunk { unsigned char fill, op, ob, kind, part, first; unsigned short col; };
+struct TrTable { TrChunk c[TR_CHUNKS]; int n; int seg[7]; };
+constexpr void tr_put(TrTable &t, int fill, int op, int ob, int col, int kind, int part, bool first) {
+  if (t.n < TR_CHUNKS)
+    t.c[t.n] = TrChunk{(unsigned char)fill, (unsigned char)op, (unsigned char)ob, (unsigned char)kind, (unsigned char)part, (unsigned char)first, (unsigned short)col};
+  ++t.n;
+}
+constexpr void tr_put_sqt(TrTable &t, int op, int col0, int slices) {               /* slices x [SQ_A SQ_B] */
+  for (int ob = 0; ob < slices; ++ob)
+    for (int j = 0; j < 2; ++j) tr_put(t, TRF_SQT, op, ob, col0, j ? SQ_B : SQ_A, 0, false);
+}
+constexpr void tr_put_plain_t(TrTable &t, int op, int col0, int slices, int kind) {  /* slices x [hi lo] */
+  for (int ob = 0; ob < slices; ++ob)
+    for (int part = 0; part < 2; ++part) tr_put(t, TRF_PLAIN_T, op, ob, col0, kind, part, false);
+}
+constexpr TrTable make_tr_table() {
+  TrTable t{};
+  /* run section: spatial ops 0..7 exactly as the eval image */
+  for (int op = 0; op < OP_HEADS; ++op)
+    for (int ob = 0; ob < 8; ++ob)
+      for (int j = 0; j < sp_slice_chunks(op, ob); ++j) tr_put(t, TRF_SQ, op, ob, op == 5 ? WIDTH : 0, sq_sp_kind(op, j), 0, j == 0);
+  t.seg[0] = t.n;
+  /* heads: 4 bottleneck slices as [SQ_A SQ_B] + the scalar block [SQ_SC] */
+  for (int ob = 0; ob < 4; ++ob)
+    for (int j = 0; j < 2; ++j) tr_put(t, TRF_SQ, OP_HEADS, ob, 0, j ? SQ_B : SQ_A, 0, j == 0);
+  tr_put(t, TRF_SQ, OP_HEADS, 4, 0, SQ_SC, 0, true);
+  t.seg[1] = t.n;
+  /* VJP: transposed spatial layers 7..1, the 96 IPE rows of layer 5 in front of layer 5, those of layer 0 at the end */
+  for (int l = 7; l >= 1; --l) {
+    if (l == 5) tr_put_sqt(t, 5, WIDTH, IPE_DIM / 32);
+    tr_put_sqt(t, l, 0, 8);
+  }
+  tr_put_sqt(t, 0, 0, IPE_DIM / 32);
+  t.seg[2] = t.n;
+  /* directional: ops 9..16 + rgb as the plain chunks of refnerf_layout.h, every chunk twice: [hi][lo] */
+  for (int op = OP_HEADS + 1; op < NUM_OPS; ++op)
+    for (int ob = 0; ob < BFPACKED.op[op].nob; ++ob)
+      for (int j = 0; j < BFPACKED.op[op].nchunk; ++j)
+        for (int part = 0; part < 2; ++part)
+          tr_put(t, TRF_PLAIN, op, ob, BFPACKED.op[op].nchunk == 2 ? WIDTH : 0, BFPACKED.op[op].kind[j], part, j == 0 && part == 0);
+  t.seg[3] = t.n;
+  /* backward: directional layers 7..1 */
+  for (int l = 7; l >= 1; --l) tr_put_plain_t(t, 9 + l, 0, 8, BF_REG);
+  t.seg[4] = t.n;
+  /* the 204 dir-input rows: 7 slices x [layer 5's part hi lo | layer 0's part hi lo] */
+  for (int ob = 0; ob < DIN_BLOCKS; ++ob)
+    for (int j = 0; j < 4; ++j) tr_put(t, TRF_PLAIN_T, j < 2 ? 14 : 9, ob, j < 2 ? WIDTH : 0, BF_REG, j & 1, false);
+  t.seg[5] = t.n;
+  /* heads^T: 8 slices x [BNLDS hi lo] */
+  tr_put_plain_t(t, OP_HEADS, 0, 8, BF_BNLDS);
+  t.seg[6] = t.n;
+  /* spatial layers 7..1 */
+  for (int l = 7; l >= 1; --l) tr_put_plain_t(t, l, 0, 8, BF_REG);
+  return t;
+}
+constexpr TrTable TR_TABLE = make_tr_table();
+static_assert(TR_TABLE.n == TR_CHUNKS, "the table fills every chunk of the image");
+static_assert(TR_TABLE.seg[0] == TR_SP_TRUNK && TR_TABLE.seg[1] == TR_SP_TRUNK + TR_HEADS && TR_TABLE.seg[2] == TR_RUN && TR_TABLE.seg[3] == TR_FWD &&
+              TR_TABLE.seg[4] == TR_BWD0 + TR_BWD_DIR && TR_TABLE.seg[5] == TR_BWD0 + TR_BWD_DIR + TR_BWD_DIN &&
+              TR_TABLE.seg[6] == TR_BWD0 + TR_BWD_DIR + TR_BWD_DIN + TR_BWD_HEADS, "the sections start where the kernels stream them from");
+/* the first TR_SP_TRUNK entries, looked up by the eval split image's own chunk index (SPPACKED: what pack_weights_split fills) */
+constexpr bool tr_trunk_is_eval_order() {
+  for (int op = 0; op < OP_HEADS; ++op) {
+    int c = SPPACKED.chunk0[op];
+    for (int ob = 0; ob < 8; ++ob)
+      for (int j = 0; j < sp_slice_chunks(op, ob); ++j, ++c) {
+        const TrChunk e = TR_TABLE.c[c];
+        if (c >= TR_SP_TRUNK || e.fill != TRF_SQ || e.op != op || e.ob != ob || e.kind != sq_sp_kind(op, j) || e.first != (j == 0)) return false;
+      }
+  }
+  return true;
+}
+static_assert(tr_trunk_is_eval_order(), "the spatial trunk of the eval image");
 
 /* ---------------- (2) ACT / DELTA ----------------
  * REFNERF_ACT_SQ: blocked units as every ACT format ([64-sample block][unit][64 samples], one dword per unit and sample):

@@ -1,7 +1,7 @@
 /*
  * refnerf_sq_train.hip -- second translation unit of librefnerf_hip.so: the round-5 training path of the parity-grade 16-bit
- * mode (REFNERF_PREC_F16X2, built-in IPE basis) on the eval kernel's skeleton.  Weight image, ACT / DELTA formats:
- * refnerf_sq_layout.h; kernels: refnerf_level_sq_fwd.h, refnerf_level_sq_bwd.h, refnerf_wgrad_sq.h.
+ * mode (REFNERF_PREC_F16X2, built-in IPE basis) on the eval kernel's skeleton.  Weight image (packed by the first unit:
+ * refnerf_pack.h), ACT / DELTA formats: refnerf_sq_layout.h; kernels: refnerf_level_sq_fwd.h, refnerf_level_sq_bwd.h, refnerf_wgrad_sq.h.
  * Entry points (C++, internal): refnerf_sq_host.h; the C ABI stays in refnerf_hip.hip.
  */
 #define REFNERF_SECONDARY_TU 1
@@ -18,184 +18,6 @@
 #include "refnerf_level_sq_fwd.h"
 #include "refnerf_level_sq_bwd.h"
 #include "refnerf_wgrad_sq.h"
-#include "refnerf_pack_common.h"
-
-namespace rn {
-
-/* ------------------------------------------------------------------ */
-/* weight image of the training kernels                               */
-/* ------------------------------------------------------------------ */
-
-/* One transposed chunk of the 16x16x32 sections (the VJP): A[row = input feature col0 + 32 ob + 16 T + r][k] = W[k][row] of
- * forward op `op`, k in the k-step order of the forward's spatial chunks (refnerf_layout.h), no bias */
-__device__ inline void fill_chunk_sqt(const float *__restrict__ P, char *__restrict__ chunk, int op, int col0, int ob, int kind) {
-  for (int e = threadIdx.x; e < 256; e += blockDim.x) reinterpret_cast<float *>(chunk)[e] = 0.0f;
-  for (int idx = threadIdx.x; idx < 16 * 512; idx += blockDim.x) {
-    const int e = idx & 7, lane = (idx >> 3) & 63, pi = idx >> 9;
-    const int bk = lane >> 4, r16 = lane & 15;
-    const int sl = pi >> 2, which = pi & 3;
-    const int T = which & 1, part = which >> 1;
-    const int st = (kind == SQ_B ? 4 : 0) + sl;
-    const int k = 32 * st + 16 * (e >> 2) + 4 * bk + (e & 3);
-    const float v = canon_w(P, op, k, col0 + ob * 32 + 16 * T + r16);
-    const _Float16 hi = (_Float16)v;
-    reinterpret_cast<_Float16 *>(chunk + 1024)[idx] = part ? (_Float16)(v - (float)hi) : hi;
-  }
-}
-/* One plain chunk of the directional trunk of the training forward: fill_chunk_plain with every weight replaced by its hi
- * (part 0) or lo (part 1) half; the bias piece only in the hi chunk that opens the slice */
-__device__ inline void fill_chunk_plain_part(const float *__restrict__ P, char *__restrict__ chunk, int op, int ob, int kind, bool first, int base, int part) {
-  for (int e = threadIdx.x; e < 256; e += blockDim.x) {
-    float v = 0.0f;
-    if (e < 32 && first) {
-      int reg = e & 15, h = e >> 4;
-      v = canon_b(P, op, ob * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * h);
-    }
-    reinterpret_cast<float *>(chunk)[e] = v;
-  }
-  for (int idx = threadIdx.x; idx < 16 * 512; idx += blockDim.x) {
-    int e = idx & 7, lane = (idx >> 3) & 63, t = idx >> 9;
-    int h = lane >> 5, row = ob * 32 + (lane & 31);
-    float v = 0.0f;
-    const bool reg_step = (kind == BF_REG) || (kind == BF_BNLDS && t < 8);
-    if (reg_step) {
-      int r = 8 * (t & 1) + e;
-      int feat = 32 * (t >> 1) + (r & 3) + 8 * (r >> 2) + 4 * h;
-      v = canon_w(P, op, row, (kind == BF_REG) ? feat : base + feat);
-    } else {
-      int kp = 16 * (t - 8) + 8 * h + e;
-      /* dir k': [Re x36 | n.v | 0 0 0 | Im x36 | 0 0 0 0] */
-      if (kp < IDE_TERMS) v = canon_w(P, op, row, base + BNECK + kp);
-      else if (kp == IDE_TERMS) v = canon_w(P, op, row, base + BNECK + IDE_DIM);
-      else if (kp >= 40 && kp < 40 + IDE_TERMS) v = canon_w(P, op, row, base + BNECK + IDE_TERMS + (kp - 40));
-    }
-    const _Float16 hi = (_Float16)v;
-    reinterpret_cast<_Float16 *>(chunk + 1024)[idx] = part ? (_Float16)(v - (float)hi) : hi;
-  }
-}
-/* One plain TRANSPOSED chunk (backward): A[row = col0 + 32 ob + lane % 32][k] = W[k][row] of forward op `op`;
- * REG: k = the 256 outputs of the layer in register-step order; HEADS (kind BF_BNLDS): k = head rows, 0..127 in register-step
- * order, then 128 + k' (k' = 16 (t - 8) + 8 h + e < 11) from the LDS tile */
-__device__ inline void fill_chunk_plain_t(const float *__restrict__ P, char *__restrict__ chunk, int op, int col0, int ob, int kind, int part) {
-  for (int e = threadIdx.x; e < 256; e += blockDim.x) reinterpret_cast<float *>(chunk)[e] = 0.0f;
-  for (int idx = threadIdx.x; idx < 16 * 512; idx += blockDim.x) {
-    int e = idx & 7, lane = (idx >> 3) & 63, t = idx >> 9;
-    int h = lane >> 5, row = col0 + ob * 32 + (lane & 31);
-    float v = 0.0f;
-    if (kind == BF_REG || t < 8) {
-      int r = 8 * (t & 1) + e;
-      int k = 32 * (t >> 1) + (r & 3) + 8 * (r >> 2) + 4 * h;
-      v = canon_w(P, op, k, row);
-    } else {
-      int kp = 16 * (t - 8) + 8 * h + e;
-      if (kp < HROWS - BNECK) v = canon_w(P, op, BNECK + kp, row);
-    }
-    const _Float16 hi = (_Float16)v;
-    reinterpret_cast<_Float16 *>(chunk + 1024)[idx] = part ? (_Float16)(v - (float)hi) : hi;
-  }
-}
-
-/* grid = TR_CHUNKS blocks of 256 threads: block c fills chunk c (refnerf_sq_layout.h) */
-__global__ void pack_train_chunks(const float *__restrict__ P, char *__restrict__ out) {
-  const int c = blockIdx.x;
-  char *chunk = out + (size_t)c * BF_CHUNK_BYTES;
-  if (c < TR_SP_TRUNK) {
-    /* spatial ops 0..7 as in the eval image */
-    int op, ob, j;
-    if (c < 8) { op = 0; ob = c; j = 0; }
-    else if (c < 72) { op = 1 + (c - 8) / 16; ob = ((c - 8) % 16) / 2; j = (c - 8) & 1; }
-    else if (c < 96) { op = 5; ob = (c - 72) / 3; j = (c - 72) % 3; }
-    else { op = 6 + (c - 96) / 16; ob = ((c - 96) % 16) / 2; j = (c - 96) & 1; }
-    const int kind = (op == 0 || j == 2) ? SQ_X : (j == 0 ? SQ_A : SQ_B);
-    fill_chunk_sq(P, chunk, op, ob, kind, j == 0, op == 5 ? WIDTH : 0);
-    return;
-  }
-  if (c < TR_SP_TRUNK + TR_HEADS) {
-    const int i = c - TR_SP_TRUNK;
-    if (i < 8) fill_chunk_sq(P, chunk, OP_HEADS, i >> 1, (i & 1) ? SQ_B : SQ_A, (i & 1) == 0, 0);
-    else fill_chunk_sq(P, chunk, OP_HEADS, 4, SQ_SC, true, 0);
-    return;
-  }
-  if (c < TR_RUN) {
-    /* VJP: L7 L6 [L5 ipe] L5 L4 L3 L2 L1 [L0 ipe] */
-    int i = c - TR_SP_TRUNK - TR_HEADS;
-    int op, col0;
-    if (i < 32) { op = 7 - i / 16; col0 = 0; i %= 16; }
-    else if (i < 38) { op = 5; col0 = WIDTH; i -= 32; }
-    else if (i < 118) { op = 5 - (i - 38) / 16; col0 = 0; i = (i - 38) % 16; }
-    else { op = 0; col0 = 0; i -= 118; }
-    fill_chunk_sqt(P, chunk, op, col0, i >> 1, (i & 1) ? SQ_B : SQ_A);
-    return;
-  }
-  if (c < TR_FWD) {
-    /* directional trunk: vd0 8 x [BN hi lo] | vd1..4 8 x [REG hi lo] | vd5 8 x [REG hi lo BN hi lo] | vd6, 7 | rgb [REG hi lo] */
-    int i = c - TR_RUN;
-    int op, ob, kind, part;
-    bool first;
-    if (i < 16) { op = 9; ob = i >> 1; kind = BF_BNLDS; part = i & 1; first = part == 0; }
-    else if (i < 80) { op = 10 + (i - 16) / 16; ob = ((i - 16) % 16) >> 1; kind = BF_REG; part = i & 1; first = part == 0; }
-    else if (i < 112) { op = 14; ob = (i - 80) >> 2; const int j = (i - 80) & 3; kind = j < 2 ? BF_REG : BF_BNLDS; part = j & 1; first = j == 0; }
-    else if (i < 144) { op = 15 + (i - 112) / 16; ob = ((i - 112) % 16) >> 1; kind = BF_REG; part = i & 1; first = part == 0; }
-    else { op = OP_RGB; ob = 0; kind = BF_REG; part = i & 1; first = part == 0; }
-    fill_chunk_plain_part(P, chunk, op, ob, kind, first, op == 14 ? WIDTH : 0, part);
-    return;
-  }
-  {
-    /* backward: dir layers 7..1 | the 204 dir-input rows: 7 x [layer 5 hi lo | layer 0 hi lo] | heads^T 8 x [hi lo] | spatial 7..1 */
-    int i = c - TR_BWD0;
-    if (i < TR_BWD_DIR) { fill_chunk_plain_t(P, chunk, 9 + 7 - i / 16, 0, (i % 16) >> 1, BF_REG, i & 1); return; }
-    i -= TR_BWD_DIR;
-    if (i < TR_BWD_DIN) { const int j = i & 3; fill_chunk_plain_t(P, chunk, j < 2 ? 14 : 9, j < 2 ? WIDTH : 0, i >> 2, BF_REG, j & 1); return; }
-    i -= TR_BWD_DIN;
-    if (i < TR_BWD_HEADS) { fill_chunk_plain_t(P, chunk, OP_HEADS, 0, i >> 1, BF_BNLDS, i & 1); return; }
-    i -= TR_BWD_HEADS;
-    fill_chunk_plain_t(P, chunk, 7 - i / 16, 0, (i % 16) >> 1, BF_REG, i & 1);
-  }
-}
-
-/* the constants block: W_density, W_rgb, and per transposed op G = max over its output rows f of sum_o |W[o][f]|;
- * grid = TRG_N blocks of 1024 threads: thread (f, rg) sums rows o = rg (mod 4) of column f with four loads in flight
- * (one thread per column walking 256 rows one dependent load at a time took 88 us of every training step; now 27) */
-__global__ __launch_bounds__(1024) void pack_train_consts(const float *__restrict__ P, float *__restrict__ K) {
-  __shared__ float red[1024];
-  const int g = blockIdx.x, f = threadIdx.x & 255, rg = threadIdx.x >> 8;
-  int op = -1, rows = WIDTH, col0 = 0, ncol = WIDTH;
-  if (g >= TRG_SP + 1 && g <= TRG_SP + 7) op = g - TRG_SP;
-  else if (g == TRG_SP5_IPE) { op = 5; col0 = WIDTH; ncol = IPE_DIM; }
-  else if (g == TRG_SP0) { op = 0; ncol = IPE_DIM; }
-  else if (g >= TRG_VD + 1 && g <= TRG_VD + 7) op = 9 + g - TRG_VD;
-  else if (g == TRG_VD5_DIN) { op = 14; col0 = WIDTH; ncol = DIR_IN; }
-  else if (g == TRG_VD0) { op = 9; ncol = DIR_IN; }
-  else if (g == TRG_HEADS) { op = OP_HEADS; rows = HROWS; }
-  else if (g == TRG_RGB) { op = OP_RGB; rows = 3; }
-  else if (g == TRG_WD) { op = OP_HEADS; rows = 1; }
-  float s[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-  if (op >= 0 && f < ncol) {
-    for (int o0 = rg; o0 < rows; o0 += 16) {
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int o = o0 + 4 * u;
-        if (o < rows) s[u] += fabsf(canon_w(P, op, g == TRG_WD ? HROW_DENSITY : o, col0 + f));
-      }
-    }
-  }
-  red[threadIdx.x] = (s[0] + s[1]) + (s[2] + s[3]);
-  __syncthreads();
-  if (rg == 0) red[f] = (red[f] + red[f + 256]) + (red[f + 512] + red[f + 768]);
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if (threadIdx.x < w) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + w]);
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) K[TRC_G + g] = red[0];
-  if (g == 0 && rg == 0) {
-    K[TRC_WD + f] = canon_w(P, OP_HEADS, HROW_DENSITY, f);
-    for (int c = 0; c < 3; ++c) K[TRC_WRGB + c * WIDTH + f] = canon_w(P, OP_RGB, c, f);
-    if (f < TRC_WRGB - TRC_G - TRG_N) K[TRC_G + TRG_N + f] = 0.0f;
-  }
-}
-
-}  // namespace rn
 
 /* ================================================================== */
 /* host                                                               */
@@ -208,16 +30,6 @@ __global__ __launch_bounds__(1024) void pack_train_consts(const float *__restric
   } while (0)
 
 namespace rnsq {
-
-size_t image_bytes() { return rn::TR_IMAGE_BYTES; }
-
-int pack(const float *d_params, void *d_packed, hipStream_t st) {
-  hipLaunchKernelGGL(rn::pack_train_chunks, dim3(rn::TR_CHUNKS), dim3(256), 0, st, d_params, (char *)d_packed);
-  hipLaunchKernelGGL(rn::pack_train_consts, dim3(rn::TRG_N), dim3(1024), 0, st, d_params,
-                     (float *)((char *)d_packed + rn::TR_CONST_OFF));
-  SQ_HIP_TRY(hipGetLastError());
-  return REFNERF_OK;
-}
 
 static int rays_per_wg_sq(int N) {
   if (N % rn::BT == 0) return 1;

@@ -14,7 +14,10 @@ The second half compares the per-sample outputs at the ragged level shapes with 
 modes with the f32 mode.  tests/test_guards_cpu.py holds the checker's self-tests and the coverage gate over CASES."""
 import ctypes as C
 import functools
+import hashlib
+import json
 import math
+import os
 
 import numpy as np
 import pytest
@@ -164,6 +167,21 @@ def _basis_np(groups):
     basis = {7: geopoly.generate_basis("icosahedron", 2), 2: geopoly.generate_basis("icosahedron", 1)}[groups]
     assert basis.shape == (3 * groups, 3)
     return f32(basis)
+
+
+def _sha(a):
+    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+
+
+@functools.lru_cache(maxsize=None)
+def _pack_digests():
+    """tests/golden/pack_digests.json (make_golden_pack_digests.py): the images' bytes as the commit named in it packed them, and
+    the digests of the inputs it packed, by this module's own _blob / _basis_np"""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "pack_digests.json")) as f:
+        want = json.load(f)
+    have = {f"blob-G{g}": _sha(_blob(g)) for g in (0, 2, 7)}
+    have.update({f"basis-G{g}": _sha(_basis_np(g)) for g in (2, 7)})
+    return want, have
 
 
 _images = {}
@@ -430,7 +448,7 @@ def _stage_cases():
     # 16-bit images: two chunks of 17 KB
     F32_PADS, CHUNK_PADS = 8 * 64 * 8 + 4 * 2048 + 8 * 2048, 2 * 17 * 1024 // 4
 
-    def pack(kind, groups):
+    def pack(id, kind, groups):
         pad_words = CHUNK_PADS if kind != _hip.PREC_F32 else F32_PADS + (8 * 64 * 8 + 8 * 2048 if groups > 1 else 0)
 
         def fn(G):
@@ -444,13 +462,20 @@ def _stage_cases():
             assert _hip.pack_weights(P, img, precision=kind, basis=basis) is img
             left = int((img.view(torch.int32) == guards.SENTINEL_I32).sum())
             assert left == pad_words, f"{left} words of the image were left alone, the layout's pads are {pad_words}"
+            want, have = _pack_digests()
+            for key in [f"blob-G{groups}"] + ([f"basis-G{groups}"] if groups > 1 else []):
+                assert have[key] == want["inputs"][key], (f"{key} is not the input tests/golden/pack_digests.json was recorded on: the INPUTS differ "
+                                                          "(synthetic / geopoly or PARAM_KW changed), this says nothing about the packer")
+            got = dict(bytes=4 * n, sha256=_sha(img.cpu().numpy()))
+            assert got == want["images"][id], (f"{id}: the packed image is {got}, commit {want['commit'][:12]} packed {want['images'][id]} from the "
+                                               "same inputs: the packer moved bytes (csrc/refnerf_pack.h)")
             return dict(image=img)
         return fn
     for name, kind in (("f32", _hip.PREC_F32), ("bf16", _hip.PREC_BF16), ("f16", _hip.PREC_F16), ("f16x2", _hip.PREC_F16X2),
                        ("f16x2_train", _hip.IMAGE_F16X2_TRAIN)):
-        CASES.append(Case(f"pack_weights-{name}", ["refnerf_pack_weights"], pack(kind, 0)))
+        CASES.append(Case(f"pack_weights-{name}", ["refnerf_pack_weights"], pack(f"pack_weights-{name}", kind, 0)))
     for groups in (2, 7):
-        CASES.append(Case(f"pack_weights_basis-G{groups}", ["refnerf_pack_weights_basis"], pack(_hip.PREC_F32, groups)))
+        CASES.append(Case(f"pack_weights_basis-G{groups}", ["refnerf_pack_weights_basis"], pack(f"pack_weights_basis-G{groups}", _hip.PREC_F32, groups)))
 
 
 _stage_cases()
