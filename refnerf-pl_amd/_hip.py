@@ -1,4 +1,4 @@
-"""ctypes binding of librefnerf_hip.so (include/refnerf_hip.h).
+"""ctypes binding of librefnerf_hip.so (include/refnerf_hip.h, and include/refnerf_distortion.h for the distortion loss).
 
 PyTorch is used only for device memory and streams: every call takes raw
 device pointers (``tensor.data_ptr()``) and the current HIP stream.  There is
@@ -38,6 +38,9 @@ CONSISTENCY_TYPES = _enum("CONSISTENCY")
 PENALTIES = _enum("PENALTY")
 VIS_CURVES = _enum("VIS_CURVE")
 VIS_OPS = _enum("VIS_OP")
+# the distortion loss has a header of its own (refnerf_hip.h and its ABI version are untouched by it): two entries, no constants
+DISTORTION_HEADER = os.path.join(os.path.dirname(_abi.HEADER), "refnerf_distortion.h")
+_distortion_prototypes = _abi.load(DISTORTION_HEADER)[2]
 LEGACY_F16X2_TRAIN = False   # the round-4 training kernels (REFNERF_LEGACY_F16X2_TRAIN) are gone; bench.py still reads this name
 IPE_MAX_GROUPS = 7           # rn::IPE_MAX_GROUPS of the library: not part of the header
 
@@ -93,12 +96,13 @@ def lib():
                 f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(the Ref-NeRF hot path has no CPU fallback)")
         L = C.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in _abi.prototypes.items():
-            try:
-                fn = getattr(L, name)
-            except AttributeError:
-                raise HipLibraryError(f"{LIB_PATH} does not export {name}, which {_abi.HEADER} declares: rebuild the library") from None
-            fn.restype, fn.argtypes = restype, argtypes
+        for header, prototypes in ((_abi.HEADER, _abi.prototypes), (DISTORTION_HEADER, _distortion_prototypes)):
+            for name, (restype, argtypes) in prototypes.items():
+                try:
+                    fn = getattr(L, name)
+                except AttributeError:
+                    raise HipLibraryError(f"{LIB_PATH} does not export {name}, which {header} declares: rebuild the library") from None
+                fn.restype, fn.argtypes = restype, argtypes
         if L.refnerf_abi_version() != ABI_VERSION:      # the loaded library against the header
             raise HipLibraryError(f"librefnerf_hip.so ABI version mismatch: {LIB_PATH} is not built from {_abi.HEADER}")
         _lib = L
@@ -781,6 +785,36 @@ def interlevel_backward(t, w, t_env, w_env, upstream):
     check(lib().refnerf_interlevel_backward(*args, _arg(upstream.reshape(1), "interlevel loss: upstream", shape=(1,), empty_null=True),
                                             ptr(g) if g.numel() else None, stream_ptr()))
     return g
+
+
+def _distortion_args(t, w):
+    if not torch.is_tensor(w) or w.dim() != 2:
+        raise ValueError("distortion loss: t [R, N+1] and w [R, N]")
+    R, N = w.shape
+    return (_arg(t, "distortion loss: t", shape=(R, N + 1), empty_null=True), _arg(w, "distortion loss: w", shape=(R, N), empty_null=True)), R, N
+
+
+def distortion_forward(t, w):
+    """refnerf_distortion_forward: stepfun.lossfun_distortion(t, w) per ray, [R] (t [R, N+1] nondecreasing, w [R, N]; contiguous
+    float32 device tensors, 1 <= N <= 512)."""
+    require_device()
+    rows, R, N = _distortion_args(t, w)
+    ray_loss = torch.empty((R,), dtype=torch.float32, device=w.device)
+    check(lib().refnerf_distortion_forward(*rows, R, N, ptr(ray_loss) if ray_loss.numel() else None, stream_ptr()))
+    return ray_loss
+
+
+def distortion_backward(t, w, g):
+    """refnerf_distortion_backward -> grad_w [R, N] = g[0] * d lossfun_distortion / d w; g: a one-element float32 device
+    tensor, the gradient of the total w.r.t. the sum of distortion_forward's per-ray values."""
+    require_device()
+    rows, R, N = _distortion_args(t, w)
+    if not torch.is_tensor(g) or g.numel() != 1:
+        raise ValueError("distortion loss: g is a one-element tensor")
+    grad_w = torch.empty((R, N), dtype=torch.float32, device=w.device)
+    check(lib().refnerf_distortion_backward(*rows, _arg(g.reshape(1), "distortion loss: g", shape=(1,)), R, N,
+                                            ptr(grad_w) if grad_w.numel() else None, stream_ptr()))
+    return grad_w
 
 
 def sample_intervals(t, logits, n, smin=0.0, smax=1.0):

@@ -230,6 +230,7 @@ class Config:
     hip_fused_losses: bool = False  # data ('mse' | 'charb', with the disparity / normal statistics) + orientation + predicted-normal losses of a level through fused kernels (train_utils.fused_refnerf_losses), and the depth smoothness of a [P, S, S, .] patch batch (train_utils.fused_depth_smoothness_loss)
     hip_fused_regularisers: bool = False  # the six geometry regularisers of a level (consistency x 4, accumulated weights, weights entropy) as ONE fused kernel each way and the noisy rays in one launch (train_utils.fused_ray_regularisers, sample_utils.sample_noisy_rays(fused=True)): no host synchronisation
     hip_fused_proposal: bool = False  # the proposal-network configuration's two host-side stages as kernels: the dilation of the step function between levels (models.Model.__call__ -> refnerf_max_dilate_weights) and the interlevel loss (train_utils.fused_interlevel_loss -> refnerf_interlevel_forward / _backward), one launch each, no host synchronisation
+    hip_distortion_loss: bool = False  # mip-NeRF 360's distortion loss on the last level, weighted by distortion_loss_mult (the reference carries the multiplier and stepfun.lossfun_distortion but its training step never calls it, so off reproduces the reference): compute_losses adds losses['distortion'] as the LAST term, through the O(N) kernels where they apply (train_utils.fused_distortion_loss -> refnerf_distortion_forward / _backward: CUDA tensors, 1..512 intervals, one launch each way) and through the O(N^2) ATen definition otherwise
     hip_flat_grads: bool = False  # route the backward's gradient to MLP.flat_parameter().grad (one tensor) instead of the 46 nn.Parameters
     # weight-gradient GEMM of the backward.  'bf16x3' (default) = the 16-bit-MFMA GEMM that goes with the chains: after f32 chains
     # (fp32 ACT / DELTA rows) operands split hi + lo into bf16 pairs, three products, fp32-level accuracy; after 'f16x2' chains

@@ -36,6 +36,29 @@ def lossfun_outer(t, w, t_env, w_env, eps=torch.finfo(torch.float32).eps):
     return torch.clamp(w - w_outer, min=0.0) ** 2 / (w + eps)
 
 
+def lossfun_distortion(t, w):
+    """mip-NeRF 360's distortion loss of the step function (t, w), per ray (stepfun.py:261-272): the double integral of
+    w_i w_j |x - y| over all pairs of intervals.  The O(N^2) definition in the reference's order of operations (bit-equal
+    values on the CPU), any device, differentiable in t and w; the hot path is refnerf_distortion_forward / _backward
+    (train_utils.fused_distortion_loss), which needs sorted knots and gives the weights' gradient only."""
+    mid = (t[..., 1:] + t[..., :-1]) / 2
+    gaps = torch.abs(mid[..., :, None] - mid[..., None, :])
+    between = torch.sum(w * torch.sum(w[..., None, :] * gaps, dim=-1), dim=-1)       # pairs of intervals
+    within = torch.sum(w ** 2 * (t[..., 1:] - t[..., :-1]), dim=-1) / 3              # an interval with itself
+    return between + within
+
+
+def interval_distortion(t0_lo, t0_hi, t1_lo, t1_hi):
+    """mean |x - y| for x uniform on [t0_lo, t0_hi] and y uniform on [t1_lo, t1_hi] (stepfun.py:275-291), in the reference's
+    order of operations."""
+    apart = torch.abs((t1_lo + t1_hi) / 2 - (t0_lo + t0_hi) / 2)                     # disjoint intervals: the midpoints' distance
+    cubes = 2 * (torch.minimum(t0_hi, t1_hi) ** 3 - torch.maximum(t0_lo, t1_lo) ** 3)
+    cross = 3 * (t1_hi * t0_hi * torch.abs(t1_hi - t0_hi) + t1_lo * t0_lo * torch.abs(t1_lo - t0_lo) +
+                 t1_hi * t0_lo * (t0_lo - t1_hi) + t1_lo * t0_hi * (t1_lo - t0_hi))
+    overlapping = (cubes + cross) / (6 * (t0_hi - t0_lo) * (t1_hi - t1_lo))
+    return torch.where((t0_lo > t1_hi) | (t1_lo > t0_hi), apart, overlapping)
+
+
 def weight_to_pdf(t, w, eps=torch.finfo(torch.float32).eps ** 2):
     """stepfun.py:92-94."""
     return w / torch.clamp(t[..., 1:] - t[..., :-1], min=eps)

@@ -336,6 +336,53 @@ def fused_interlevel_loss(ray_history, config):
     return config.interlevel_loss_mult * total
 
 
+def distortion_loss(ray_history, config):
+    """mip-NeRF 360's distortion loss on the last level (Config.hip_distortion_loss; the reference's stepfun.lossfun_distortion,
+    which its own training step never calls): the O(N^2) ATen definition, [R, N, N] intermediates under autograd."""
+    from . import stepfun
+    last = ray_history[-1]
+    return config.distortion_loss_mult * torch.mean(stepfun.lossfun_distortion(last['sdist'], last['weights']))
+
+
+class _FusedDistortion(torch.autograd.Function):
+    """sum over rays of stepfun.lossfun_distortion(t, w) as a single autograd node on refnerf_distortion_forward / _backward:
+    O(N) per ray on the sorted knots, t and w read once, one launch each way.  Only w gets a gradient: every sdist the model
+    emits is detached, and the kernels do not compute the knots' gradient."""
+
+    @staticmethod
+    def forward(ctx, t, w):
+        from . import _hip
+        rows = tuple(x.detach().to(torch.float32).reshape(-1, x.shape[-1]).contiguous() for x in (t, w))
+        ctx.rows, ctx.shape = rows, w.shape
+        return _hip.distortion_forward(*rows).sum()
+
+    @staticmethod
+    def backward(ctx, g_sum):
+        from . import _hip
+        # the upstream gradient stays on the device (no host synchronisation)
+        g = _hip.distortion_backward(*ctx.rows, g_sum.detach().to(torch.float32).reshape(1).contiguous())
+        return None, g.reshape(ctx.shape)
+
+
+_DISTORTION_MAX_INTERVALS = 512     # refnerf_distortion_forward / _backward: N in [1, 512]
+
+
+def fused_distortion_supported(ray_history):
+    """The kernels take CUDA tensors of 1..512 intervals on the last level."""
+    h = ray_history[-1]
+    return bool(h['weights'].is_cuda and h['sdist'].is_cuda and 1 <= h['weights'].shape[-1] <= _DISTORTION_MAX_INTERVALS and
+                h['sdist'].shape[-1] == h['weights'].shape[-1] + 1)
+
+
+def fused_distortion_loss(ray_history, config):
+    """distortion_loss through the fused kernels: the same value (fp32 summation order aside: the kernel's recurrence has no
+    cancellation, the ATen midpoint differences do) and the same gradient into the last level's weights."""
+    last = ray_history[-1]
+    w = last['weights']
+    rays = w.numel() // w.shape[-1]
+    return config.distortion_loss_mult * (_FusedDistortion.apply(last['sdist'].detach(), w) / float(rays))
+
+
 _REG_TERMS = ('weights_entropy', 'acc', 'diffuse_consistency', 'specular_consistency', 'normals_consistency',
               'distance_consistency')        # the order of the kernels' scales / of the node's per-term output
 _REG_INPUTS = ('weights', 'acc', 'distance', 'diffuse', 'specular', 'normals')
@@ -681,7 +728,8 @@ def compute_losses(model, batch, rays, renderings, ray_history, config, renderin
     """The loss assembly of NeRFSystem.training_step (nerf_system.py:118-180) on already computed
     renderings: returns (total, dict of terms, stats).  Config.hip_fused_losses / hip_fused_regularisers route the three Ref-NeRF
     terms / the six geometry regularisers through their fused kernels and Config.hip_fused_proposal the interlevel loss through
-    its own (same keys, same order).  Config.hip_fused_losses also covers the 'charb' penalty, the linear-rgb target, the
+    its own (same keys, same order); Config.hip_distortion_loss appends mip-NeRF 360's distortion loss of the last level as
+    losses['distortion'] when Config.distortion_loss_mult > 0.  Config.hip_fused_losses also covers the 'charb' penalty, the linear-rgb target, the
     disparity / normal statistics (the reference's stats keys in the reference's order) and the depth smoothness of a
     [P, S, S, .] patch batch; the geometry regularisers want flat batches, so a patch batch keeps their ATen path."""
     losses = {}
@@ -732,6 +780,11 @@ def compute_losses(model, batch, rays, renderings, ray_history, config, renderin
     if want_entropy:
         losses['weights_entropy'] = reg['weights_entropy'] if fused_reg else \
             weights_entropy_loss(model, renderings, ray_history, config, warmup_ratio)
+    if getattr(config, 'hip_distortion_loss', False) and config.distortion_loss_mult > 0:
+        # opt-in, and the LAST key: no other term moves in the summation order.  One launch each way where the kernels apply
+        # (refnerf_distortion_forward / _backward), the ATen definition elsewhere (CPU tensors, more than 512 intervals)
+        losses['distortion'] = fused_distortion_loss(ray_history, config) if fused_distortion_supported(ray_history) else \
+            distortion_loss(ray_history, config)
     total = torch.sum(torch.stack([torch.as_tensor(v, dtype=torch.float32, device=data_loss.device)
                                    for v in losses.values()]))
     if getattr(config, 'hip_check_finite', True):
