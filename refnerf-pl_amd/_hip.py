@@ -1,4 +1,5 @@
-"""ctypes binding of librefnerf_hip.so (include/refnerf_hip.h, and include/refnerf_distortion.h for the distortion loss).
+"""ctypes binding of librefnerf_hip.so (include/refnerf_hip.h, include/refnerf_distortion.h for the distortion loss and
+include/refnerf_tsdf.h for geometry export).
 
 PyTorch is used only for device memory and streams: every call takes raw
 device pointers (``tensor.data_ptr()``) and the current HIP stream.  There is
@@ -41,6 +42,10 @@ VIS_OPS = _enum("VIS_OP")
 # the distortion loss has a header of its own (refnerf_hip.h and its ABI version are untouched by it): two entries, no constants
 DISTORTION_HEADER = os.path.join(os.path.dirname(_abi.HEADER), "refnerf_distortion.h")
 _distortion_prototypes = _abi.load(DISTORTION_HEADER)[2]
+# geometry export likewise: TSDF fusion and marching tetrahedra, one struct (the voxel grid), four entries
+TSDF_HEADER = os.path.join(os.path.dirname(_abi.HEADER), "refnerf_tsdf.h")
+_tsdf_constants, _tsdf_structs, _tsdf_prototypes = _abi.load(TSDF_HEADER)
+TsdfGrid = _tsdf_structs["refnerf_tsdf_grid"]
 LEGACY_F16X2_TRAIN = False   # the round-4 training kernels (REFNERF_LEGACY_F16X2_TRAIN) are gone; bench.py still reads this name
 IPE_MAX_GROUPS = 7           # rn::IPE_MAX_GROUPS of the library: not part of the header
 
@@ -96,7 +101,8 @@ def lib():
                 f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(the Ref-NeRF hot path has no CPU fallback)")
         L = C.CDLL(LIB_PATH)
-        for header, prototypes in ((_abi.HEADER, _abi.prototypes), (DISTORTION_HEADER, _distortion_prototypes)):
+        for header, prototypes in ((_abi.HEADER, _abi.prototypes), (DISTORTION_HEADER, _distortion_prototypes),
+                                   (TSDF_HEADER, _tsdf_prototypes)):
             for name, (restype, argtypes) in prototypes.items():
                 try:
                     fn = getattr(L, name)
@@ -815,6 +821,73 @@ def distortion_backward(t, w, g):
     check(lib().refnerf_distortion_backward(*rows, _arg(g.reshape(1), "distortion loss: g", shape=(1,)), R, N,
                                             ptr(grad_w) if grad_w.numel() else None, stream_ptr()))
     return grad_w
+
+
+def tsdf_grid(dims, origin, voxel_size, trunc) -> TsdfGrid:
+    """The host struct of a voxel grid: dims (nx, ny, nz), origin the centre of voxel (0, 0, 0)."""
+    g = TsdfGrid()
+    g.nx, g.ny, g.nz = (int(d) for d in dims)
+    g.origin[0], g.origin[1], g.origin[2] = (float(o) for o in origin)
+    g.voxel_size, g.trunc = float(voxel_size), float(trunc)
+    return g
+
+
+def tsdf_integrate(grid: TsdfGrid, tsdf, weight, rgb, pixtocam, camtoworlds, frame, depth, acc=None, acc_min=0.0, view_rgb=None,
+                   view_weight=1.0, z_min=0.0):
+    """refnerf_tsdf_integrate: fuses the view depth [H,W] (acc [H,W], view_rgb [H,W,3] optional) of pose `frame` of
+    camtoworlds [F,3,4] into tsdf / weight [nz,ny,nx] and rgb [nz,ny,nx,3] (or None), in place.  All contiguous float32
+    device tensors, every shape checked here."""
+    require_device()
+    dev, vox = tsdf.device if torch.is_tensor(tsdf) else None, (grid.nz, grid.ny, grid.nx)
+    if not torch.is_tensor(depth) or depth.dim() != 2:
+        raise ValueError("tsdf_integrate: depth [H, W]")
+    H, W = depth.shape
+    if not torch.is_tensor(camtoworlds) or camtoworlds.dim() != 3:
+        raise ValueError("tsdf_integrate: camtoworlds [F, 3, 4]")
+    what = "tsdf_integrate: "
+    check(lib().refnerf_tsdf_integrate(
+        C.byref(grid), _arg(tsdf, what + "tsdf", shape=vox), _arg(weight, what + "weight", shape=vox, device=dev),
+        _arg(rgb, what + "rgb", shape=vox + (3,), device=dev, optional=True), _arg(pixtocam, what + "pixtocam", shape=(3, 3), device=dev),
+        _arg(camtoworlds, what + "camtoworlds", shape=(camtoworlds.shape[0], 3, 4), device=dev), camtoworlds.shape[0], int(frame),
+        W, H, _arg(depth, what + "depth", device=dev), _arg(acc, what + "acc", shape=(H, W), device=dev, optional=True), float(acc_min),
+        _arg(view_rgb, what + "view_rgb", shape=(H, W, 3), device=dev, optional=True), float(view_weight), float(z_min), stream_ptr()))
+
+
+def tsdf_mesh_workspace_bytes(grid: TsdfGrid) -> int:
+    return int(lib().refnerf_tsdf_mesh_workspace_bytes(C.byref(grid)))
+
+
+def tsdf_mesh_count(grid: TsdfGrid, tsdf, weight, iso=0.0, min_weight=1.0, workspace=None):
+    """refnerf_tsdf_mesh_count -> (workspace, counts): the byte workspace refnerf_tsdf_mesh_emit reads and the device
+    int64[2] {n_vertices, n_triangles}."""
+    require_device()
+    vox = (grid.nz, grid.ny, grid.nx)
+    nbytes = tsdf_mesh_workspace_bytes(grid)
+    t = _arg(tsdf, "tsdf_mesh_count: tsdf", shape=vox)
+    if workspace is None:
+        workspace = torch.empty(nbytes, dtype=torch.uint8, device=tsdf.device)
+    counts = torch.empty(2, dtype=torch.int64, device=tsdf.device)
+    check(lib().refnerf_tsdf_mesh_count(C.byref(grid), t, _arg(weight, "tsdf_mesh_count: weight", shape=vox, device=tsdf.device),
+                                        float(iso), float(min_weight), _arg(workspace, "tsdf_mesh_count: workspace", dtype=torch.uint8),
+                                        workspace.numel(), ptr(counts), stream_ptr()))
+    return workspace, counts
+
+
+def tsdf_mesh_emit(grid: TsdfGrid, tsdf, rgb, iso, workspace, n_vertices: int, n_triangles: int):
+    """refnerf_tsdf_mesh_emit -> (vertices [V,3] float32, vertex_rgb [V,3] float32 or None without `rgb`, triangles [T,3]
+    int32); the counts are the host values of tsdf_mesh_count's."""
+    require_device()
+    vox, dev = (grid.nz, grid.ny, grid.nx), tsdf.device if torch.is_tensor(tsdf) else None
+    V, T = int(n_vertices), int(n_triangles)
+    t = _arg(tsdf, "tsdf_mesh_emit: tsdf", shape=vox)
+    vertices = torch.empty((V, 3), dtype=torch.float32, device=dev)
+    colors = None if rgb is None else torch.empty((V, 3), dtype=torch.float32, device=dev)
+    triangles = torch.empty((T, 3), dtype=torch.int32, device=dev)
+    check(lib().refnerf_tsdf_mesh_emit(C.byref(grid), t, _arg(rgb, "tsdf_mesh_emit: rgb", shape=vox + (3,), device=dev, optional=True),
+                                       float(iso), _arg(workspace, "tsdf_mesh_emit: workspace", dtype=torch.uint8, device=dev),
+                                       workspace.numel(), V, T, ptr(vertices) if V else None,
+                                       ptr(colors) if colors is not None and V else None, ptr(triangles) if T else None, stream_ptr()))
+    return vertices, colors, triangles
 
 
 def sample_intervals(t, logits, n, smin=0.0, smax=1.0):
