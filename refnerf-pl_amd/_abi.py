@@ -1,11 +1,15 @@
 """The C ABI of librefnerf_hip.so as ctypes, read from include/refnerf_hip.h: the header is the single source.
 
-parse(text) -> (constants, structs, prototypes):
+parse(text, structs=None, constants=None) -> (constants, structs, prototypes):
   constants   {name: int}: every `#define REFNERF_* <integer expression>` and every enumerator;
   structs     {name: ctypes.Structure subclass}: every `typedef struct`, in header order;
   prototypes  {name: (restype, [argtypes])}: every function.
 The parser is strict: comments, the include guard, #include and the `extern "C"` bracket are dropped on purpose, and
 whatever else it does not understand raises HeaderError with the offending text -- nothing is skipped.
+`structs` and `constants` seed the tables with what an included header declared: parse itself opens no file, so a text that
+says `#include "sibling.h"` and names the sibling's types needs them.  load(path) does that: it parses every quoted include
+(a header in the same directory) first, seeds the includer with its structs and constants, and returns the includer's own
+prototypes -- an entry belongs to the header that declares it.
 """
 import ctypes as C
 import os
@@ -74,8 +78,8 @@ def _declarations(text, constants, structs, arrays=True):
     return out
 
 
-def parse(text):
-    constants, structs, prototypes = {}, {}, {}
+def parse(text, structs=None, constants=None):
+    constants, structs, prototypes = dict(constants or {}), dict(structs or {}), {}
     text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
     text = re.sub(r"#ifdef __cplusplus\b.*?#endif", " ", text, flags=re.S)       # the extern "C" bracket
     # declarations end at a `;` outside braces; preprocessor lines stand alone.  Both kinds keep their order, so that an
@@ -101,7 +105,7 @@ def parse(text):
             m = re.match(r"#\s*define\s+(\w+)\s+(\S.*)$", item)
             if m:
                 constants[m.group(1)] = _int(m.group(2), constants)
-            elif not re.match(r"#\s*(ifndef\s+\w+|define\s+\w+|endif|include\s*<\w+\.h>)$", item):
+            elif not re.match(r"#\s*(ifndef\s+\w+|define\s+\w+|endif|include\s*<\w+\.h>|include\s*\"\w+\.h\")$", item):
                 raise HeaderError(f"unsupported preprocessor line {item!r}")
             continue
         m = re.match(r"enum \{(.*)\}$", item)
@@ -130,11 +134,25 @@ def parse(text):
     return constants, structs, prototypes
 
 
-def load(path=HEADER):
+_loaded = {}       # normalised path -> what load() parsed: a struct is one ctypes class, whichever header's load reaches it
+
+
+def load(path=HEADER, _including=()):
     if not os.path.exists(path):
         raise HipLibraryError(f"{path} is missing: the ctypes binding is read from the C header")
-    with open(path) as f:
-        return parse(f.read())
+    path = os.path.normpath(os.path.abspath(path))
+    if path in _including:
+        raise HeaderError(f"{path} includes itself")
+    if path not in _loaded:
+        with open(path) as f:
+            text = f.read()
+        constants, structs = {}, {}
+        for name in re.findall(r'^[ \t]*#\s*include\s*"(\w+\.h)"', re.sub(r"/\*.*?\*/", " ", text, flags=re.S), flags=re.M):
+            c, s, _ = load(os.path.join(os.path.dirname(path), name), _including + (path,))
+            constants.update(c)
+            structs.update(s)
+        _loaded[path] = parse(text, structs, constants)
+    return tuple(dict(table) for table in _loaded[path])
 
 
 constants, structs, prototypes = load()

@@ -1,5 +1,5 @@
-"""ctypes binding of librefnerf_hip.so (include/refnerf_hip.h, include/refnerf_distortion.h for the distortion loss and
-include/refnerf_tsdf.h for geometry export).
+"""ctypes binding of librefnerf_hip.so (include/refnerf_hip.h, include/refnerf_distortion.h for the distortion loss,
+include/refnerf_tsdf.h for geometry export and include/refnerf_raycast.h for views of the exported volume).
 
 PyTorch is used only for device memory and streams: every call takes raw
 device pointers (``tensor.data_ptr()``) and the current HIP stream.  There is
@@ -46,6 +46,10 @@ _distortion_prototypes = _abi.load(DISTORTION_HEADER)[2]
 TSDF_HEADER = os.path.join(os.path.dirname(_abi.HEADER), "refnerf_tsdf.h")
 _tsdf_constants, _tsdf_structs, _tsdf_prototypes = _abi.load(TSDF_HEADER)
 TsdfGrid = _tsdf_structs["refnerf_tsdf_grid"]
+# the ray caster of the fused volume: a header that includes refnerf_tsdf.h for the grid struct (the same class as TsdfGrid:
+# _abi.load parses a header once), one entry of its own
+RAYCAST_HEADER = os.path.join(os.path.dirname(_abi.HEADER), "refnerf_raycast.h")
+_raycast_prototypes = _abi.load(RAYCAST_HEADER)[2]
 LEGACY_F16X2_TRAIN = False   # the round-4 training kernels (REFNERF_LEGACY_F16X2_TRAIN) are gone; bench.py still reads this name
 IPE_MAX_GROUPS = 7           # rn::IPE_MAX_GROUPS of the library: not part of the header
 
@@ -102,7 +106,7 @@ def lib():
                 "(the Ref-NeRF hot path has no CPU fallback)")
         L = C.CDLL(LIB_PATH)
         for header, prototypes in ((_abi.HEADER, _abi.prototypes), (DISTORTION_HEADER, _distortion_prototypes),
-                                   (TSDF_HEADER, _tsdf_prototypes)):
+                                   (TSDF_HEADER, _tsdf_prototypes), (RAYCAST_HEADER, _raycast_prototypes)):
             for name, (restype, argtypes) in prototypes.items():
                 try:
                     fn = getattr(L, name)
@@ -888,6 +892,33 @@ def tsdf_mesh_emit(grid: TsdfGrid, tsdf, rgb, iso, workspace, n_vertices: int, n
                                        workspace.numel(), V, T, ptr(vertices) if V else None,
                                        ptr(colors) if colors is not None and V else None, ptr(triangles) if T else None, stream_ptr()))
     return vertices, colors, triangles
+
+
+def tsdf_raycast(grid: TsdfGrid, tsdf, weight, rgb, pixtocam, camtoworlds, frame, width, height, iso=0.0, min_weight=1.0, step=0.5,
+                 refine=4, t_near=0.0, t_far=float("inf")):
+    """refnerf_tsdf_raycast -> (depth [H,W], normals [H,W,3], view_rgb [H,W,3] or None without `rgb`, acc [H,W]): the view of
+    pose `frame` of camtoworlds [F,3,4] through pixtocam [3,3] of the volume tsdf / weight [nz,ny,nx], rgb [nz,ny,nx,3] (or
+    None).  All contiguous float32 device tensors, every shape checked here; `step` in voxels."""
+    require_device()
+    dev, vox = tsdf.device if torch.is_tensor(tsdf) else None, (grid.nz, grid.ny, grid.nx)
+    if not torch.is_tensor(camtoworlds) or camtoworlds.dim() != 3:
+        raise ValueError("tsdf_raycast: camtoworlds [F, 3, 4]")
+    W, H = int(width), int(height)
+    if W < 1 or H < 1:
+        raise ValueError("tsdf_raycast: width and height must be positive")
+    what = "tsdf_raycast: "
+    t = _arg(tsdf, what + "tsdf", shape=vox)
+    depth = torch.empty((H, W), dtype=torch.float32, device=dev)
+    normals = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
+    view_rgb = None if rgb is None else torch.empty((H, W, 3), dtype=torch.float32, device=dev)
+    acc = torch.empty((H, W), dtype=torch.float32, device=dev)
+    check(lib().refnerf_tsdf_raycast(
+        C.byref(grid), t, _arg(weight, what + "weight", shape=vox, device=dev),
+        _arg(rgb, what + "rgb", shape=vox + (3,), device=dev, optional=True), _arg(pixtocam, what + "pixtocam", shape=(3, 3), device=dev),
+        _arg(camtoworlds, what + "camtoworlds", shape=(camtoworlds.shape[0], 3, 4), device=dev), camtoworlds.shape[0], int(frame),
+        W, H, float(iso), float(min_weight), float(step), int(refine), float(t_near), float(t_far), ptr(depth), ptr(normals),
+        ptr(view_rgb), ptr(acc), stream_ptr()))
+    return depth, normals, view_rgb, acc
 
 
 def sample_intervals(t, logits, n, smin=0.0, smax=1.0):

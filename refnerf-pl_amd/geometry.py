@@ -6,10 +6,14 @@ include/refnerf_tsdf.h, and this module is its interface:
     geometry.fuse_views(lambda rays: model(rays, 1., True), dataset, config, volume)
     vertices, faces, colors = volume.extract_mesh()
     geometry.save_ply('mesh.ply', vertices, faces, colors)
+    view = volume.raycast_view(dataset, 0)                  # depth, normals, rgb, acc of the surface seen by a camera
+    scores = geometry.surface_metrics(volume, dataset)      # normals_mae against the dataset's normals, coverage
 
 On a HIP device both stages are the kernels of csrc/refnerf_tsdf.h (no fallback: a missing library raises).  With
 device='cpu' the volume runs the float64 restatement below -- the header's lines in its order, rounded once to float32 --
-which the kernels reproduce bit for bit; `integrate_aten` is the same restatement on tensors of any device."""
+which the kernels reproduce bit for bit; `integrate_aten` is the same restatement on tensors of any device.  The ray caster
+that renders the volume back into images is include/refnerf_raycast.h: csrc/refnerf_raycast.h on the device, `raycast_host`
+here."""
 import itertools
 
 import numpy as np
@@ -141,6 +145,116 @@ def extract_mesh_host(dims, origin, voxel_size, tsdf, weight, rgb, iso=0.0, min_
     return vertices, triangles, colors
 
 
+def raycast_host(dims, origin, voxel_size, tsdf, weight, rgb, pixtocam, camtoworld, width, height, iso=0.0, min_weight=1.0, step=0.5,
+                 refine=4, t_near=0.0, t_far=float('inf')):
+    """refnerf_tsdf_raycast of include/refnerf_raycast.h on numpy arrays tsdf / weight [nz,ny,nx], rgb [nz,ny,nx,3] or None,
+    pixtocam [3,3], camtoworld [3,4]: (depth [H,W], normals [H,W,3], rgb [H,W,3] or None, acc [H,W]) float32, the header's
+    lines in its order in float64, vectorised over the pixels with a loop over the sample index k, bit for bit."""
+    f64 = np.float64
+    nx, ny, nz = (int(n) for n in dims)
+    n = (nx, ny, nz)
+    W, H = int(width), int(height)
+    flat = np.ascontiguousarray(tsdf, np.float32).reshape(-1)
+    seen = np.ascontiguousarray(weight, np.float32).reshape(-1) >= np.float32(min_weight)
+    colour = None if rgb is None else np.ascontiguousarray(rgb, np.float32).reshape(-1, 3)
+    org = [f64(np.float32(v)) for v in origin]
+    h, iso, step = f64(np.float32(voxel_size)), f64(np.float32(iso)), f64(np.float32(step))
+    K, M = np.asarray(pixtocam, np.float32).astype(f64), np.asarray(camtoworld, np.float32).astype(f64)
+    sy, sz = nx, nx * ny
+    corner = np.array([(m & 1) + (m >> 1 & 1) * sy + (m >> 2 & 1) * sz for m in range(8)], np.int64)
+
+    def cell(o, d, t):
+        """SAMPLE: (corner values [8,n], fr [3,n], valid [n], cell index [n]) at o + t d"""
+        i, fr = [], []
+        for a in range(3):
+            g = ((o[a] + t * d[a]) - org[a]) / h
+            f = np.floor(g)
+            ia = np.where(f > 0, np.where(f < n[a] - 2, f, f64(n[a] - 2)), 0.0)       # a NaN gives 0
+            i.append(ia.astype(np.int64))
+            fr.append(g - ia)
+        p = (i[2] * sz + i[1] * sy) + i[0]
+        q = p[None, :] + corner[:, None]
+        return flat[q].astype(f64), fr, seen[q].all(0), p
+
+    def lerp3(c, fr):
+        x = [c[2 * q] + fr[0] * (c[2 * q + 1] - c[2 * q]) for q in range(4)]
+        y = [x[2 * r] + fr[1] * (x[2 * r + 1] - x[2 * r]) for r in range(2)]
+        return y[0] + fr[2] * (y[1] - y[0])
+
+    with np.errstate(all='ignore'):
+        px, py = np.meshgrid(np.arange(W, dtype=f64) + .5, np.arange(H, dtype=f64) + .5, indexing='xy')
+        px, py = px.reshape(-1), py.reshape(-1)
+        cx = K[0, 0] * px + K[0, 1] * py + K[0, 2]
+        cy = -(K[1, 0] * px + K[1, 1] * py + K[1, 2])
+        cz = f64(-1.0)
+        d = [M[a, 0] * cx + M[a, 1] * cy + M[a, 2] * cz for a in range(3)]
+        o = [M[a, 3] for a in range(3)]
+        t0, t1 = np.full(px.shape, f64(np.float32(t_near))), np.full(px.shape, f64(np.float32(t_far)))
+        miss = np.zeros(px.shape, bool)
+        for a in range(3):
+            lo, hi = org[a], org[a] + f64(n[a] - 1) * h
+            zero = d[a] == 0
+            if not (lo <= o[a] and o[a] <= hi):
+                miss |= zero
+            ta, tb = (lo - o[a]) / d[a], (hi - o[a]) / d[a]
+            lo_t, hi_t = np.where(ta < tb, ta, tb), np.where(ta > tb, ta, tb)
+            t0 = np.where(zero, t0, np.where(t0 > lo_t, t0, lo_t))
+            t1 = np.where(zero, t1, np.where(t1 < hi_t, t1, hi_t))
+        miss |= ~(t1 >= t0)
+        dt = step * h / np.sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2])
+        N = np.floor((t1 - t0) / dt)
+        miss |= ~(N <= f64(nx + ny + nz) / step)
+
+        # MARCH over the rays still looking for their bracket; `ray` indexes the pixels
+        ray = np.flatnonzero(~miss)
+        prev, v_prev, t_prev = np.zeros(ray.size, bool), np.zeros(ray.size), np.zeros(ray.size)
+        hits, brackets = [], []
+        k = 0
+        while ray.size:
+            go = N[ray] >= k
+            ray, prev, v_prev, t_prev = ray[go], prev[go], v_prev[go], t_prev[go]
+            if not ray.size:
+                break
+            t = t0[ray] + f64(k) * dt[ray]
+            c, fr, ok, _ = cell(o, [d[a][ray] for a in range(3)], t)
+            v = lerp3(c, fr) - iso
+            hit = ok & prev & (v_prev >= 0) & (v < 0)
+            if hit.any():
+                hits.append(ray[hit])
+                brackets.append(np.stack([t_prev[hit], t[hit], v_prev[hit], v[hit]]))
+            prev, v_prev, t_prev = ok, np.where(ok, v, v_prev), np.where(ok, t, t_prev)
+            keep = ~hit
+            ray, prev, v_prev, t_prev = ray[keep], prev[keep], v_prev[keep], t_prev[keep]
+            k += 1
+
+        depth, acc = np.zeros(H * W, np.float32), np.zeros(H * W, np.float32)
+        normals = np.zeros((H * W, 3), np.float32)
+        view_rgb = None if colour is None else np.zeros((H * W, 3), np.float32)
+        if hits:
+            ray = np.concatenate(hits)
+            a_t, b_t, fa, fb = np.concatenate(brackets, 1)
+            dr = [d[a][ray] for a in range(3)]
+            for _ in range(int(refine)):                                 # REFINE
+                tm = 0.5 * (a_t + b_t)
+                c, fr, _, _ = cell(o, dr, tm)
+                vm = lerp3(c, fr) - iso
+                neg = vm < 0
+                a_t, fa, b_t, fb = np.where(neg, a_t, tm), np.where(neg, fa, vm), np.where(neg, tm, b_t), np.where(neg, vm, fb)
+            ts = a_t + (fa / (fa - fb)) * (b_t - a_t)                    # HIT
+            c, fr, _, p = cell(o, dr, ts)
+            u = [1.0 - fr[a] for a in range(3)]
+            gx = u[1] * u[2] * (c[1] - c[0]) + fr[1] * u[2] * (c[3] - c[2]) + u[1] * fr[2] * (c[5] - c[4]) + fr[1] * fr[2] * (c[7] - c[6])
+            gy = u[0] * u[2] * (c[2] - c[0]) + fr[0] * u[2] * (c[3] - c[1]) + u[0] * fr[2] * (c[6] - c[4]) + fr[0] * fr[2] * (c[7] - c[5])
+            gz = u[0] * u[1] * (c[4] - c[0]) + fr[0] * u[1] * (c[5] - c[1]) + u[0] * fr[1] * (c[6] - c[2]) + fr[0] * fr[1] * (c[7] - c[3])
+            s = np.sqrt(gx * gx + gy * gy + gz * gz)
+            depth[ray], acc[ray] = ts.astype(np.float32), 1.0
+            normals[ray] = np.where((s > 0)[:, None], np.stack([gx / s, gy / s, gz / s], -1), 0.0).astype(np.float32)
+            if colour is not None:
+                q = p[None, :] + corner[:, None]
+                view_rgb[ray] = np.stack([lerp3(colour[q, ch].astype(f64), fr) for ch in range(3)], -1).astype(np.float32)
+    return (depth.reshape(H, W), normals.reshape(H, W, 3), None if view_rgb is None else view_rgb.reshape(H, W, 3), acc.reshape(H, W))
+
+
 def _camera_tuple(cameras):
     """(pixtocams, camtoworlds, distortion_params, pixtocam_ndc, spherical) of a PathCameras / SceneDataset or of the
     reference's camera tuple"""
@@ -265,11 +379,110 @@ class TSDFVolume:
             vertices, colors, faces = _hip.tsdf_mesh_emit(self.grid, self.tsdf, self.rgb, iso, workspace, n_vertices, n_triangles)
         return vertices, faces, colors
 
+    def raycast(self, pixtocam, camtoworld, width, height, iso=0., min_weight=1., step=0.5, refine=4, near=0., far=float('inf')):
+        """The volume seen by a pinhole camera (include/refnerf_raycast.h): a dict of `depth` [H,W] -- the distance along the
+        unnormalised ray directions, what `integrate` takes --, `normals` [H,W,3] (unit, towards free space), `rgb` [H,W,3]
+        (colour volumes only) and `acc` [H,W] (1 on a hit; a miss is all zero), float32 on the volume's device.  The march
+        takes `step` voxels at a time through the cells whose corners all have weight >= min_weight, from `near` to `far`
+        along the ray, and bisects the first crossing from free space into the surface `refine` times."""
+        what = 'TSDFVolume.raycast: '
+        W, H = int(width), int(height)
+        if W != width or H != height or W < 1 or H < 1:
+            raise ValueError(what + f'width and height must be positive integers, got {width!r} x {height!r}')
+        if not (np.isfinite(iso) and np.isfinite(min_weight)):
+            raise ValueError(what + 'iso and min_weight must be finite')
+        if not 1 / 64 <= float(np.float32(step)) <= 64:
+            raise ValueError(what + f'step must lie in [1/64, 64] voxels, got {step!r}')
+        if int(refine) != refine or not 0 <= int(refine) <= 32:
+            raise ValueError(what + f'refine must be an integer in [0, 32], got {refine!r}')
+        if not near >= 0 or np.isnan(far):
+            raise ValueError(what + 'near must be >= 0 and far must not be NaN')
+        c2w = torch.as_tensor(np.asarray(camtoworld, np.float32) if not torch.is_tensor(camtoworld) else camtoworld)
+        if c2w.dim() != 2 or c2w.shape[0] < 3 or c2w.shape[1] != 4:
+            raise ValueError(what + f'camtoworld must be [3, 4] or [4, 4], got {tuple(c2w.shape)}')
+        p2c = torch.as_tensor(np.asarray(pixtocam, np.float32) if not torch.is_tensor(pixtocam) else pixtocam)
+        if tuple(p2c.shape) != (3, 3):
+            raise ValueError(what + f'pixtocam must be [3, 3], got {tuple(p2c.shape)}')
+        c2w = c2w[:3, :4].detach().to(device=self.device, dtype=torch.float32).contiguous()
+        p2c = p2c.detach().to(device=self.device, dtype=torch.float32).contiguous()
+        if self.device.type == 'cpu':
+            out = raycast_host(self.dims, self.origin, self.voxel_size, self.tsdf.numpy(), self.weight.numpy(),
+                               None if self.rgb is None else self.rgb.numpy(), p2c.numpy(), c2w.numpy(), W, H, iso, min_weight, step,
+                               int(refine), near, far)
+            depth, normals, view_rgb, acc = (None if a is None else torch.from_numpy(a) for a in out)
+        else:
+            with torch.cuda.device(self.device):
+                depth, normals, view_rgb, acc = _hip.tsdf_raycast(self.grid, self.tsdf, self.weight, self.rgb, p2c, c2w[None], 0, W, H, iso,
+                                                                  min_weight, step, int(refine), near, far)
+        out = dict(depth=depth, normals=normals, acc=acc)
+        if view_rgb is not None:
+            out['rgb'] = view_rgb
+        return out
 
-def fuse_views(render_fn, cameras, config, volume, indices=None, depth_key='distance_median', **kw):
+    def raycast_view(self, cameras, idx, width=None, height=None, **kw):
+        """`raycast` of view `idx` of `cameras` (a PathCameras / SceneDataset, or the reference's camera tuple).  The image
+        size is the dataset's; a bare tuple needs `width=` and `height=`."""
+        pixtocams, camtoworlds, distortion, ndc, spherical = _camera_tuple(cameras)
+        if ndc is not None:
+            raise ValueError('TSDF ray casting: pixtocam_ndc is set: depths of NDC space are not metric')
+        if distortion is not None:
+            raise ValueError('TSDF ray casting: distortion_params is set: lens-distorted views are not ray cast')
+        if spherical:
+            raise ValueError('TSDF ray casting: spherical (panorama) cameras are not ray cast')
+        width = getattr(cameras, 'width', None) if width is None else width
+        height = getattr(cameras, 'height', None) if height is None else height
+        if width is None or height is None:
+            raise ValueError('TSDF ray casting: a camera tuple carries no image size: give width= and height=')
+        # the one view is indexed where the stacks live (tensors stay on their device), `raycast` moves it to the volume's
+        p2c, c2w = (x if torch.is_tensor(x) else np.asarray(x, np.float32) for x in (pixtocams, camtoworlds))
+        return self.raycast(p2c[idx] if p2c.ndim == 3 else p2c, c2w[idx][:3, :4], int(width), int(height), **kw)
+
+
+def surface_metrics(volume, dataset, indices=None, renderings=None, depth_key='distance_median', **kw):
+    """Scores of the exported surface against a dataset's views `indices` (default: all), each ray cast with
+    `volume.raycast_view(dataset, idx, **kw)`:
+        normals_mae  image.compute_weighted_mae(acc * alphas, normals, the dataset's normals), in degrees -- the score of the
+                     model's normals, on the surface's; present when the dataset has `normal_images` and `alphas`;
+        depth_l1     the mean of |depth - renderings[idx][depth_key]| over the pixels where both have acc >= 0.5; present when
+                     `renderings` (a dict or sequence indexed by view, of what models.render_image returned) is given;
+        coverage     the mean of acc.
+    Returns dict(views={idx: {...}}, and each key's mean over the views that have it), float64 host scalars: nothing but the
+    scalars leaves the device, in one transfer at the end."""
+    from . import image
+    indices = [int(i) for i in (range(dataset.size) if indices is None else indices)]
+    normals_gt, alphas = getattr(dataset, 'normal_images', None), getattr(dataset, 'alphas', None)
+    keys, rows = ['coverage'], []
+    if normals_gt is not None and alphas is not None:
+        keys.append('normals_mae')
+    if renderings is not None:
+        keys.append('depth_l1')
+    for idx in indices:
+        view = volume.raycast_view(dataset, idx, **kw)
+        acc, dev = view['acc'], view['acc'].device
+        row = dict(coverage=acc.double().mean())
+        if 'normals_mae' in keys:
+            w = acc * torch.as_tensor(alphas[idx], dtype=torch.float32, device=dev).reshape(acc.shape)
+            gt = torch.as_tensor(normals_gt[idx], dtype=torch.float32, device=dev).reshape(view['normals'].shape)
+            row['normals_mae'] = image.compute_weighted_mae(w.contiguous(), view['normals'], gt.contiguous()).double().reshape(())
+        if 'depth_l1' in keys:
+            r = renderings[idx]
+            r_acc = torch.as_tensor(r['acc'], dtype=torch.float32, device=dev).reshape(acc.shape)
+            r_depth = torch.as_tensor(r[depth_key], dtype=torch.float32, device=dev).reshape(acc.shape)
+            both = ((acc >= 0.5) & (r_acc >= 0.5)).double()
+            row['depth_l1'] = ((view['depth'].double() - r_depth.double()).abs() * both).sum() / both.sum()
+        rows.append(torch.stack([row[k] for k in keys]))
+    table = torch.stack(rows).cpu().numpy() if rows else np.zeros((0, len(keys)))
+    out = dict(views={idx: {k: float(table[r, c]) for c, k in enumerate(keys)} for r, idx in enumerate(indices)})
+    for c, k in enumerate(keys):
+        out[k] = float(np.nanmean(table[:, c])) if len(indices) and not np.isnan(table[:, c]).all() else float('nan')
+    return out
+
+
+def fuse_views(render_fn, cameras, config, volume, indices=None, depth_key='distance_median', keep=None, **kw):
     """Render the views `indices` (default: all) of `cameras` -- anything with `.size`, `generate_ray_batch(idx)` and
     `.cameras` -- with `models.render_image` and fuse each into `volume`; renderings stay on the device.  `render_fn(rays)`
-    is the eval forward, e.g. `lambda rays: model(rays, 1., True)`.  Returns the volume."""
+    is the eval forward, e.g. `lambda rays: model(rays, 1., True)`.  `keep`: a dict that receives, per view index, the
+    rendering's `depth_key` and 'acc' -- what `surface_metrics` compares the surface's depth with.  Returns the volume."""
     from . import models
     _camera_tuple(cameras)
     for idx in (range(cameras.size) if indices is None else indices):
@@ -277,7 +490,33 @@ def fuse_views(render_fn, cameras, config, volume, indices=None, depth_key='dist
         with torch.no_grad():
             rendering = models.render_image(render_fn, batch.rays, config, verbose=False, device=batch.rays.origins.device)
         volume.integrate_rendering(rendering, cameras, int(idx), depth_key=depth_key, **kw)
+        if keep is not None:
+            keep[int(idx)] = {depth_key: rendering[depth_key], 'acc': rendering['acc']}
     return volume
+
+
+def write_surface_views(volume, cameras, out_dir, indices=None, **kw):
+    """Ray cast the views `indices` (default: all) of `cameras` and write, per view, `surface_normals_<idx>.png` (n / 2 + .5,
+    misses black) and `surface_depth_<idx>.png` (the hits' depths scaled to [0, 1] over the view, near bright, misses black)
+    through the writer `models.render_path` uses (utils.save_img_u8), named like its artefacts.  Returns the paths written."""
+    import os
+    from . import utils
+    indices = [int(i) for i in (range(cameras.size) if indices is None else indices)]
+    zpad = max(3, len(str(max(indices, default=0))))
+    os.makedirs(out_dir, exist_ok=True)
+    done = []
+    for idx in indices:
+        view = volume.raycast_view(cameras, idx, **kw)
+        depth, acc = view['depth'], view['acc']
+        hit = acc > 0
+        lo = torch.where(hit, depth, torch.full_like(depth, float('inf'))).min()
+        hi = (depth * acc).max()
+        panel = torch.where(hit, 1 - (depth - lo) / torch.clamp(hi - lo, min=torch.finfo(torch.float32).tiny), torch.zeros_like(depth))
+        s = str(idx).zfill(zpad)
+        for img, name in (((view['normals'] / 2 + .5) * acc[..., None], f'surface_normals_{s}.png'), (panel, f'surface_depth_{s}.png')):
+            utils.save_img_u8(img, os.path.join(out_dir, name))
+            done.append(os.path.join(out_dir, name))
+    return done
 
 
 def save_ply(path, vertices, faces, colors=None):

@@ -3,8 +3,13 @@ iso-surface as a binary PLY (refnerf_pl_amd.geometry; include/refnerf_tsdf.h):
     python scripts/extract_mesh.py --gin_configs configs/refnerf_blender.gin --ckpt model.ckpt --data_dir scene/ --out mesh.ply
 --ckpt is a checkpoint of the reference's Lightning system (utils.load_reference_checkpoint); without it the model keeps its
 initial weights (a plumbing run).  The views are those of --split, pinhole and undistorted (NDC, lens distortion and
-panoramas raise).  --aabb is the box the volume covers, in the frame the model was trained in."""
+panoramas raise).  --aabb is the box the volume covers, in the frame the model was trained in.
+--surface_metrics ray casts the fused volume back into the same views (include/refnerf_raycast.h) and prints
+geometry.surface_metrics: the angular error of the surface's normals against the split's ground-truth normals (where the
+scene has them), the L1 distance of its depth to the rendered --depth_key, the coverage.  --surface_dir DIR writes the normal
+and depth panels of those views."""
 import argparse
+import json
 import os
 import sys
 
@@ -28,6 +33,8 @@ def main(argv=None):
     ap.add_argument("--min_weight", type=float, default=1.0, help="a cell needs this much weight on all eight corners")
     ap.add_argument("--max_views", type=int, default=None)
     ap.add_argument("--no_color", action="store_true")
+    ap.add_argument("--surface_metrics", action="store_true", help="print the scores of the ray-cast surface for the fused split")
+    ap.add_argument("--surface_dir", default=None, help="write surface_normals_ / surface_depth_ panels of the ray-cast views here")
     args = ap.parse_args(argv)
 
     import torch
@@ -47,12 +54,20 @@ def main(argv=None):
     views = datasets.load_dataset(args.split, args.data_dir, cfg, device=dev)
     volume = geometry.TSDFVolume(args.aabb[:3], args.aabb[3:], resolution=args.resolution, trunc=args.trunc, color=not args.no_color, device=dev)
     indices = range(views.size if args.max_views is None else min(views.size, args.max_views))
+    renderings = {} if args.surface_metrics else None
     geometry.fuse_views(lambda rays: model(rays, 1.0, True), views, cfg, volume, indices=indices, depth_key=args.depth_key,
-                        acc_threshold=args.acc_threshold)
+                        keep=renderings, acc_threshold=args.acc_threshold)
     vertices, faces, colors = volume.extract_mesh(min_weight=args.min_weight)
     geometry.save_ply(args.out, vertices, faces, colors)
     print(f"{args.out}: {vertices.shape[0]} vertices, {faces.shape[0]} triangles from {len(indices)} views "
           f"({volume.dims[0]} x {volume.dims[1]} x {volume.dims[2]} voxels of {volume.voxel_size:g})")
+    cast = dict(min_weight=args.min_weight)
+    if args.surface_metrics:
+        scores = geometry.surface_metrics(volume, views, indices=indices, renderings=renderings, depth_key=args.depth_key, **cast)
+        print(json.dumps(scores))
+    if args.surface_dir:
+        written = geometry.write_surface_views(volume, views, args.surface_dir, indices=indices, **cast)
+        print(f"{args.surface_dir}: {len(written)} files")
     return 0
 
 
